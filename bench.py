@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — distinct states/s and time-to-first-violation of the GPU BFS model checker on BASELINE.json's configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline alone: set-up, W warm-up runs, K timed runs, the result line.  --full adds everything else this file
+measures or checks: the untimed verification run and the second-hash audit, the config2 / config4 / config5 objects and the CPU
+baseline.  --dump-outputs DIR (N = 1) writes what the last timed run computed as DIR/*.npy (float64; 64-bit values split into two exact
+32-bit halves): per-level figures, per-action successor counts, fingerprint checksums of the levels beyond the record buffers, the
+counter-example and a summary row — the same for every run of the same arguments, so two builds can be compared output for output.
 
 N = 1.  The headline is the configuration north_star quotes the metric on and that fits one MI355X: the reference README's state-
 transfer-defect configuration (BASELINE.json configs[2]: ReplicaCount=3, ClientCount=1, Values={v1,v2,v3}, StartViewOnTimerLimit=3,
@@ -27,7 +33,8 @@ Extra objects on the JSON line: `roofline` for the dominant kernel (k_expand: al
 stream; `traffic` = the committed PMC figure when it was measured on THIS build's kernel sources, else null), `cpu_baseline` = the
 CPU oracle (a port, not TLC) timed on this box's host cores on a bounded sample of the headline's configuration,
 `fingerprint_collision_estimate` (the birthday bound n^2 / 2^65 and TLC's d (g - d) / 2^64) and `collision_audit` (the untimed verification runs repeated under a second member
-of the fingerprint family, vsrmc_model_set_fp_seed: every per-level count must equal the oracle fixture's under both).
+of the fingerprint family, vsrmc_model_set_fp_seed: every per-level count must equal the oracle fixture's under both).  `cpu_baseline`,
+`collision_audit`, `reference_trace_in_this_run` and the config objects are --full figures.
 """
 import argparse
 import json
@@ -105,6 +112,41 @@ def cpu_baseline(seconds=15.0, cfg=None):
 AUDIT_SEED = 0x5EED5EED5EED5EED                       # second-hash audit: every count of the verification run once more under this fp_seed
 
 
+def _split64(x):
+    """uint64 values -> float64 [..., 2] (high, low 32-bit halves): exact, where one float64 would round them."""
+    import numpy as np
+    a = np.asarray(x, dtype=np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def run_outputs(rows, tr, distinct, depth, viol_fp):
+    """What a caller of the timed path receives from one run, as float64 arrays (--dump-outputs).  rows: one (level dict, kind) per
+    unit of progress, kind "level" (stored), "deep" (seen-set only: its fingerprint checksums) or "probe" (the probed level: successors
+    only); tr: the counter-example [(action name, wire record)]."""
+    import numpy as np
+    from vsr_tlaplus_amd.checker import ACTION_NAMES
+    cols = ("level", "n_new", "generated", "deadlocks", "max_bag", "viol_mask")
+    levels = np.array([[float(d[c]) if kind != "probe" or c in ("level", "generated", "viol_mask") else 0.0 for c in cols]
+                       for d, kind in rows], dtype=np.float64)
+    acts = np.array([[float(x) for x in d["act_generated"][1:16]] for d, _kind in rows], dtype=np.float64)
+    sums = np.array([[d["fp_xor"], d["fp_sum"]] if kind == "deep" else [0, 0] for d, kind in rows], dtype=np.uint64)
+    recs = [np.asarray(rec, dtype=np.uint64) for _a, rec in tr]
+    return {"levels": levels,                                             # columns: level, new states, generated, deadlocks, largest bag, violation mask
+            "act_generated": acts,                                        # successors per action (ACTION_NAMES[1:16]) of every row of `levels`
+            "fp_checksums": _split64(sums).reshape(len(rows), 4),         # xor hi, lo, sum hi, lo (0 for stored and probed levels)
+            "trace_actions": np.array([ACTION_NAMES.index(a) for a, _r in tr], dtype=np.float64),
+            "trace_offsets": np.cumsum([0] + [len(r) for r in recs]).astype(np.float64),
+            "trace_words": _split64(np.concatenate(recs)),
+            "summary": np.concatenate([np.array([distinct, depth, len(tr)], dtype=np.float64), _split64(viol_fp)])}
+
+
+def dump_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_single(args, seed=0):
     """BASELINE configs[1] through the automatic level scheme (ModelChecker.advance: every level fits the record buffers here).
     seed != 0: one untimed run under another member of the fingerprint family — every count must equal the fixture's (the
@@ -122,9 +164,11 @@ def run_single(args, seed=0):
         mc.reset()
         t0 = time.perf_counter()
         cur_words = int(m.layout.fixed_words) + int(m.layout.permutations)      # Init record, device layout
+        rows = []
         while True:
             kind, d, _ = mc.advance()
             assert kind == "level", "config 2 fits the record buffers of one MI355X"
+            rows.append((d, kind))
             want = EXPECT["levels"][d["level"] - 1] if d["n_new"] else None     # every run, every level: the oracle's figures
             assert want is None or (d["n_new"], d["generated"], d["deadlocks"], d["max_bag"]) == \
                 (want["new"], want["generated"], want["deadlocks"], want["max_bag"]), (d["level"], d["n_new"], d["generated"])
@@ -156,6 +200,7 @@ def run_single(args, seed=0):
         if record:
             S["distinct"] += mc.distinct
             S["ttfv"].append(dt)
+            S["last"] = (rows, tr, mc.distinct, mc.level, mc.violation["fp"])    # what this run computed (--dump-outputs)
 
     try:
         if seed:
@@ -281,11 +326,15 @@ def run_readme(args, dump_trace=None, seed=0):
         split = {k_: [0.0, 0.0, 0] for k_ in ("stored", "virtual", "regenerate", "insert_beyond", "probe")}
         s_rec, n_prev = 8.0 * cur_words, 1                                   # bytes per record / states of the newest level
         passes = []
+        rows = []                                                            # what the run computed, level by level (--dump-outputs)
         found = None
         while found is None:
             kind, a, b = mc.advance()
             want = check_level(a, verify)
             gen += a["generated"]
+            rows.append((a, kind))
+            if b is not None:
+                rows.append((b, "probe"))
             if kind == "level":
                 if verify and want["fp_xor"] is not None and E["checksums"] and not seed:
                     x, sm, cnt = mc.level_checksum()
@@ -384,6 +433,7 @@ def run_readme(args, dump_trace=None, seed=0):
             S["launches"] = launches
             S["deep"] = passes
             S["split"] = split
+            S["last"] = (rows, tr, mc.distinct, found["level"], found["viol_fp"])
 
     try:
         if seed:
@@ -601,28 +651,40 @@ def main():
     ap.add_argument("--no-config4", action="store_true", help="skip the config-4 object (BASELINE configs[3] under assume_commit_number)")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 object (BASELINE configs[4]: 14 oracle-pinned levels + the probe of level 15, two seeds)")
     ap.add_argument("--workload", choices=["auto", "readme", "config3", "config2"], default="auto",
-                    help="auto (default): the README defect configuration (BASELINE configs[2], fits one MI355X) is the headline and config 2 "
-                         "(BASELINE configs[1]) an object beside it; readme / config3: only the former; config2: only the latter")
+                    help="auto (default): the README defect configuration (BASELINE configs[2], fits one MI355X) is the headline and, with "
+                         "--full, config 2 (BASELINE configs[1]) an object beside it; readme / config3: only the former; config2: only the latter")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the untimed verification run and the second-hash audit, the "
+                         "config2 / config4 / config5 objects, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed run computed as DIR/<name>.npy (float64; N = 1)")
     args = ap.parse_args()
+    if not args.full:                                                        # a plain run: the headline alone
+        args.no_verify = args.no_cpu_baseline = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 or world > 1 or os.environ.get("VSR_BENCH_SHARDED"):   # VSR_BENCH_SHARDED=1: the N > 1 leg on one rank
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the N = 1 leg only")
         from vsr_tlaplus_amd import sharded_bench
         return sharded_bench.main(args, sys.modules[__name__])
     want_readme = args.workload in ("auto", "readme", "config3") and not args.no_config3
-    want_c2 = args.workload in ("auto", "config2") and not args.no_config2
+    want_c2 = args.workload in ("auto", "config2") and not args.no_config2 and (args.full or not want_readme)
     c2 = rd = c4 = c5 = None
     audit = None
     if want_c2:
         elapsed, S, _ = run_single(args)
         c2 = config2_object(args, elapsed, S)
+        last = S["last"]
     if want_readme:
         # a README leg that cannot run (e.g. another process holds the HBM) is an ERROR of the bench, not a reason to print another workload's
         # number under the headline: the exception propagates and the exit code is not 0
         elapsed, S = run_readme(args, os.environ.get("VSR_BENCH_DUMP_TRACE"))
         rd = readme_object(args, elapsed, S)
-    if args.workload == "auto" and not args.no_config4 and not args.no_config3:
+        last = S["last"]
+    if args.dump_outputs:                                                    # the headline's last timed run
+        dump_outputs(run_outputs(*last), args.dump_outputs)
+    if args.full and args.workload == "auto" and not args.no_config4 and not args.no_config3:
         c4 = run_config4(args)
-    if args.workload == "auto" and not args.no_config5 and not args.no_config3:
+    if args.full and args.workload == "auto" and not args.no_config5 and not args.no_config3:
         c5 = run_config5(args)
     if not args.no_verify:
         # second-hash audit: the untimed verification runs once more under another member of the fingerprint family — every per-level count

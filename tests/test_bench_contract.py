@@ -23,7 +23,7 @@ def test_expectations_come_from_the_oracle_fixture():
 def test_flags_of_the_contract_parse():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--no-config3", "--no-cpu-baseline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--no-config3", "--no-cpu-baseline", "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 
@@ -38,3 +38,24 @@ def test_cpu_baseline_leg_and_loud_failure_without_a_gpu():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-config3"],
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and not any(l.startswith("{") for l in r.stdout.splitlines()), r.stdout[-500:]
+
+
+def test_dumped_outputs_are_exact_float64(tmp_path):
+    """--dump-outputs: 64-bit fingerprints and record words survive as two exact 32-bit halves, every array is written as float64."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = (1 << 64) - 3
+    row = dict(level=2, n_new=5, generated=9, deadlocks=1, max_bag=3, viol_mask=0, act_generated=list(range(16)), fp_xor=big, fp_sum=7)
+    rows = [(row, "level"), (row, "deep"), (dict(row, n_new=0, viol_mask=1), "probe")]
+    tr = [("Initial predicate", np.array([1, big], dtype=np.uint64)), ("SendDVC", np.array([1 << 40], dtype=np.uint64))]
+    out = bench.run_outputs(rows, tr, 100, 3, big)
+    bench.dump_outputs(out, str(tmp_path))
+    got = {n: np.load(str(tmp_path / (n + ".npy"))) for n in out}
+    assert all(a.dtype == np.float64 for a in got.values())
+    w = got["trace_words"]
+    assert [int(h) << 32 | int(lo) for h, lo in w] == [1, big, 1 << 40] and list(got["trace_offsets"]) == [0, 2, 3]
+    assert list(got["trace_actions"]) == [0, 4]
+    assert list(got["fp_checksums"][1]) == [big >> 32, big & 0xFFFFFFFF, 0, 7] and not got["fp_checksums"][0].any()
+    assert list(got["levels"][2]) == [2, 0, 9, 0, 0, 1] and got["act_generated"].shape == (3, 15)
+    assert int(got["summary"][3]) << 32 | int(got["summary"][4]) == big

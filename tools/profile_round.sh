@@ -40,5 +40,5 @@ one sq_counters_readme_b "--workload readme" --kernel-trace --pmc SQ_INSTS_VMEM 
 $R/tools/kernel_resources.sh $R/vsr_tlaplus_amd/libvsrmc.so k_expandILb1ELi31 > $OUT/${TAG}_kernel_resources.txt 2>&1
 rm -f $OUT/${TAG}_*.db
 # the driver-style line last: its roofline.traffic comes from the request counters measured above on the same sources
-python $R/bench.py --steps 5 --warmup 1 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python $R/bench.py --full --steps 5 --warmup 1 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 1200 $OUT/${TAG}_bench.json
