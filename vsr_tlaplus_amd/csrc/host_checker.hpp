@@ -104,96 +104,57 @@ struct vsrmc_checker {
 namespace {
 typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*, u64, u64*, u64, LevelCtl*, int, int, u64*, u64, u32, u64*,
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
-// k_expand<true, SPEC>: the configurations of BASELINE.json (and their small neighbours used by the tests) have their own
-// instantiation with the model constants folded in; anything else runs the generic one.
-ExpandKernel exact_kernel_for(const Model& M) {               // two-kernel levels: k_expand<false, SPEC>
-  if (M.model_id == 1) return k_expand<false, 1000>;
-  if (M.model_id == 2) return k_expand<false, 2000>;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 211: return k_expand<false, 211>;
-    case 312: return k_expand<false, 312>;
-    case 313: return k_expand<false, 313>;
-    case 512: return k_expand<false, 512>;
-    default: return k_expand<false, 0>;
-  }
-}
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,
                                   const uint8_t*, u64*, u64*, int, u32, u32, int, const u64*);
-MaterializeKernel materialize_kernel_for(const Model& M) {
-  if (M.model_id == 1) return k_materialize<1000>;
-  if (M.model_id == 2) return k_materialize<2000>;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 211: return k_materialize<211>;
-    case 312: return k_materialize<312>;
-    case 313: return k_materialize<313>;
-    case 512: return k_materialize<512>;
-    default: return k_materialize<0>;
-  }
+// Every instantiation of k_expand and k_materialize, by configuration.  The configurations of BASELINE.json (and their small neighbours used by
+// the tests) have instantiations with the model constants folded in; anything else runs the model's generic ones (SPEC % 1000 == 0).
+struct KernelSet {
+  ExpandKernel exact;                   // two-kernel levels: k_expand<false, SPEC> ...
+  MaterializeKernel materialize;        // ... and k_materialize<SPEC>
+  ExpandKernel fused;                   // single-pass levels: every mode, sharded or not
+  bool generic;                         // `fused` is generic in the constants (fused_shape: the only one that may run 128-record tiles at R <= 3)
+  // unsharded passes (k_expand: EXPAND_*), or null where the configuration has none
+  ExpandKernel plain = nullptr, plain5 = nullptr, modes = nullptr, regen_bits = nullptr, insert = nullptr, probe = nullptr;
+};
+template <int SPEC>
+KernelSet full_set(ExpandKernel plain5 = nullptr) {             // a model-0 configuration with the whole family of unsharded instantiations
+  return {k_expand<false, SPEC>, k_materialize<SPEC>, k_expand<true, SPEC>, false, k_expand<true, SPEC, EXPAND_PLAIN>, plain5,
+          k_expand<true, SPEC, EXPAND_MODES>, k_expand<true, SPEC, EXPAND_REGEN_BITS>, k_expand<true, SPEC, EXPAND_INSERT>, k_expand<true, SPEC, EXPAND_PROBE>};
 }
-ExpandKernel plain_kernel_for(const Model& M) {               // unsharded ordinary levels: modes and sharding compiled out
-  if (M.model_id == 1) return (M.R == 3 && M.n == 2) ? k_expand<true, 1302, true> : nullptr;   // the shipped VR_STATE_TRANSFER.cfg
-  if (M.model_id == 2) return (M.R == 3 && M.n == 2) ? k_expand<true, 2302, true> : nullptr;   // the shipped VR_APP_STATE.cfg
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 312: return k_expand<true, 312, true>;
-    case 313: return k_expand<true, 313, true>;
-    case 512: return k_expand<true, 512, true>;
-    default: return nullptr;
+KernelSet kernels_for(const Model& M) {
+  switch (M.model_id * 1000 + M.R * 100 + M.C * 10 + M.n) {     // (the models 1 and 2 have no clients: C = 0)
+    case 211: return {k_expand<false, 211>, k_materialize<211>, k_expand<true, 211>, false};
+    case 212: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 212>, false};
+    case 311: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 311>, false};
+    case 312: return full_set<312>(k_expand<true, 312, EXPAND_PLAIN5>);   // BASELINE configs[1]: its ordinary level fits 96 registers (two permutations)
+    case 313: return full_set<313>();
+    case 323: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 323>, false};
+    case 412: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 412>, false};
+    case 512: return full_set<512>();
+    case 1302: {                                                 // the shipped VR_STATE_TRANSFER.cfg
+      KernelSet k{k_expand<false, 1000>, k_materialize<1000>, k_expand<true, 1302>, false};
+      k.plain = k_expand<true, 1302, EXPAND_PLAIN>;
+      return k;
+    }
+    case 2302: {                                                 // the shipped VR_APP_STATE.cfg
+      KernelSet k{k_expand<false, 2000>, k_materialize<2000>, k_expand<true, 2302>, false};
+      k.plain = k_expand<true, 2302, EXPAND_PLAIN>;
+      return k;
+    }
   }
-}
-ExpandKernel plain5_kernel_for(const Model& M) {              // the ordinary level at five blocks per CU: pays where the kernel fits 96 registers (two permutations: 107 -> 7 spilled)
-  if (M.model_id != 0 || std::getenv("VSRMC_NO_OCC5")) return nullptr;
-  return (M.R * 100 + M.C * 10 + M.n) == 312 ? k_expand<true, 312, 5> : nullptr;
-}
-ExpandKernel modes_kernel_for(const Model& M) {               // unsharded passes with a mode (probe / virtual / regenerated / streamed levels)
-  if (M.model_id != 0) return nullptr;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 312: return k_expand<true, 312, 2>;
-    case 313: return k_expand<true, 313, 2>;
-    case 512: return k_expand<true, 512, 2>;
-    default: return nullptr;
-  }
-}
-// one mode compiled in (k_expand: PLAIN == 3 / 4): which = MODE_REGEN (by the claim bitmap) or MODE_INSERT
-ExpandKernel one_mode_kernel_for(const Model& M, int which) {
-  if (M.model_id != 0) return nullptr;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 312: return which == MODE_REGEN ? k_expand<true, 312, 3> : k_expand<true, 312, 4>;
-    case 313: return which == MODE_REGEN ? k_expand<true, 313, 3> : k_expand<true, 313, 4>;
-    case 512: return which == MODE_REGEN ? k_expand<true, 512, 3> : k_expand<true, 512, 4>;
-    default: return nullptr;
-  }
-}
-ExpandKernel probe_kernel_for(const Model& M) {
-  if (M.model_id != 0 || std::getenv("VSRMC_NO_PROBE_KERNEL")) return nullptr;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 312: return k_expand<true, 312, 6>;
-    case 313: return k_expand<true, 313, 6>;
-    case 512: return k_expand<true, 512, 6>;
-    default: return nullptr;
-  }
-}
-ExpandKernel fused_kernel_for(const Model& M) {
-  if (M.model_id == 1) return (M.R == 3 && M.n == 2) ? k_expand<true, 1302> : k_expand<true, 1000>;
-  if (M.model_id == 2) return (M.R == 3 && M.n == 2) ? k_expand<true, 2302> : k_expand<true, 2000>;
-  switch (M.R * 100 + M.C * 10 + M.n) {
-    case 211: return k_expand<true, 211>;
-    case 212: return k_expand<true, 212>;
-    case 311: return k_expand<true, 311>;
-    case 312: return k_expand<true, 312>;
-    case 313: return k_expand<true, 313>;
-    case 323: return k_expand<true, 323>;
-    case 412: return k_expand<true, 412>;
-    case 512: return k_expand<true, 512>;
-    default: return k_expand<true, 0>;
-  }
+  if (M.model_id == 1) return {k_expand<false, 1000>, k_materialize<1000>, k_expand<true, 1000>, true};
+  if (M.model_id == 2) return {k_expand<false, 2000>, k_materialize<2000>, k_expand<true, 2000>, true};
+  return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 0>, true};
 }
 // Launch shape of the single-pass kernel for one launch.  The LDS slot of a record only has to hold the longest record of the
 // level that is being expanded (stride = fixed words + its largest bag, made odd: conflict-free columns), not the format's
 // worst case, so deep levels of small bags leave room for more resident blocks.  64-record tiles when that gives at least
 // three blocks per CU (registers and LDS, asked from the runtime), else 128-record tiles (R <= 3) at two.
-#ifndef VSR_CCAP64          // work-list entries of a 64-record tile, R <= 3 (24 per record; an overflow is ERR_FRONTIER_FULL, never silent)
-#define VSR_CCAP64 1536
-#endif
+constexpr u32 VSR_CCAP64 = 1536;   // work-list entries of a 64-record tile, R <= 3 (24 per record; an overflow is ERR_FRONTIER_FULL, never silent)
+// The largest LDS per block measured to run FIVE resident blocks per CU: the runtime's occupancy query is necessary, not sufficient — 32.3 KB per block
+// (a work list of 1024 entries) runs as FOUR resident blocks although the query says five.  (The sweep of DESIGN.md §8.5: config 2 k_expand 132.7 / 132.9 /
+// 132.5 / 131.2 / 141.2 ms at 512 / 640 / 768 / 896 / 1024 entries, 137.1 with the four-block instantiation.)
+constexpr size_t LDS5_MAX = 31744;
 struct FusedShape {
   int blk;
   int tile;
@@ -223,51 +184,28 @@ FusedShape fused_shape(vsrmc_checker* c, u64 max_bag_of_source, bool plain = fal
   const int occ64 = occupancy(64, ccap64, &lds64);
   // 128-record tiles: only the instantiations that are generic in the constants (compiled for two blocks per CU) ever have fewer than three 64-record
   // tiles resident at R <= 3 — the specialised ones size their per-record LDS arrays for 64 (vsr_kernels.hpp: TILE_MAX)
-  const bool generic = kernel == (const void*)(ExpandKernel)k_expand<true, 0> || kernel == (const void*)(ExpandKernel)k_expand<true, 1000> ||
-                       kernel == (const void*)(ExpandKernel)k_expand<true, 2000>;
+  const bool generic = kernel == c->fused_kernel && kernels_for(M).generic;
   const int occ128 = (M.R <= 3 && generic) ? occupancy(128, 1536u, &lds128) : 0;
   if (M.R <= 3 && occ64 < 3 && occ128 >= 1) {
     f.tile = 128; f.ccap = 1536u; f.lds = lds128; f.blocks_per_cu = (unsigned)std::min(occ128, 2);
   } else {
     f.tile = 64; f.ccap = ccap64; f.lds = lds64; f.blocks_per_cu = (unsigned)std::max(1, std::min(occ64, VSR_OCC + 1));   // (what the instantiation's registers and this LDS allow)
   }
-#if VSR_TILE128
-  if (plain && M.R <= 3) {                                       // EXPERIMENT: 128-record tiles, a work list of 1024 (8 per record; overflow goes to the host's list), three blocks per CU
-    size_t l128 = 0;
-    const int o128 = occupancy(128, 1024u, &l128);
-    if (o128 >= 3) { f.tile = 128; f.ccap = 1024u; f.lds = l128; f.blocks_per_cu = 3; f.kernel = kernel; return f; }
-  }
-#endif
   f.kernel = kernel;
   // FIVE blocks per CU: the configuration has an ordinary-level instantiation compiled for 96 registers (plain5_kernel), and this launch's tile plus a
   // work list of 896 entries (14 instances per record; the mean is 5 — a tile with more is written down and launched again in halves:
-  // redo_overflowed_tiles) fits the LDS five times.  The runtime's occupancy query is necessary, not sufficient: 32.3 KB per block (1024 entries) runs as FOUR
-  // resident blocks although the query says five — 31.3 KB (896) is the largest size measured at five (VSRMC_LDS5 / VSRMC_CCAP5: the sweep of DESIGN.md §8.5:
-  // config 2 k_expand 132.7 / 132.9 / 132.5 / 131.2 / 141.2 ms at 512 / 640 / 768 / 896 / 1024 entries, 137.1 with the four-block instantiation).
+  // redo_overflowed_tiles) fits the LDS five times (LDS5_MAX).
   if (plain && c->plain5_kernel && M.R <= 3 && f.tile == 64) {
-    static const u32 cc5 = std::getenv("VSRMC_CCAP5") ? (u32)std::max(256, std::atoi(std::getenv("VSRMC_CCAP5"))) & ~127u : 896u;
-    static const size_t lds5 = std::getenv("VSRMC_LDS5") ? (size_t)std::atoll(std::getenv("VSRMC_LDS5")) : (size_t)31744;
+    const u32 cc5 = 896;
     hipFuncAttributes at;
     size_t dyn = (size_t)64 * f.stride * 8 + 2 * (size_t)cc5 * 4;
     int nb5 = 0;
-    if (hipFuncGetAttributes(&at, c->plain5_kernel) == hipSuccess && dyn + at.sharedSizeBytes <= lds5 &&
+    if (hipFuncGetAttributes(&at, c->plain5_kernel) == hipSuccess && dyn + at.sharedSizeBytes <= LDS5_MAX &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb5, c->plain5_kernel, blk, dyn) == hipSuccess && nb5 >= VSR_OCC + 1) {
       f.kernel = c->plain5_kernel; f.ccap = cc5; f.lds = dyn; f.blocks_per_cu = (unsigned)(VSR_OCC + 1);
     }
   }
-  if (const char* e = std::getenv("VSRMC_MAX_BPC"))            // diagnostic: fewer resident blocks per CU (occupancy sweeps)
-    f.blocks_per_cu = (unsigned)std::max(1, std::min<int>((int)f.blocks_per_cu, std::atoi(e)));
   return f;
-}
-
-// The seen-set's memory.  EXPERIMENT KNOB (environment, read per allocation): VSRMC_TABLE_MEM=uncached | finegrained allocates it with
-// hipExtMallocWithFlags(hipDeviceMallocUncached | hipDeviceMallocFinegrained) — every probe misses the caches anyway (the table is 100 x the L2 + Infinity
-// Cache), and a cached 16-byte probe drags a 128-byte line through the fabric; unset = hipMalloc (the product's default).
-hipError_t table_alloc(Slot** out, u64 slots) {
-  const char* e = std::getenv("VSRMC_TABLE_MEM");
-  if (e && std::strcmp(e, "uncached") == 0) return hipExtMallocWithFlags((void**)out, slots * sizeof(Slot), hipDeviceMallocUncached);
-  if (e && std::strcmp(e, "finegrained") == 0) return hipExtMallocWithFlags((void**)out, slots * sizeof(Slot), hipDeviceMallocFinegrained);
-  return hipMalloc((void**)out, slots * sizeof(Slot));
 }
 
 // the winner set of a sharded deep search: allocated at the first pass beyond the record buffers, half as many slots as the seen-set (the memory
@@ -284,7 +222,6 @@ int wset_ensure(vsrmc_checker* c) {
     return 0;
   }
   u64 slots = std::max<u64>((u64)1 << 12, (c->tmask + 1) / 2);
-  if (const char* e = std::getenv("VSRMC_WSET_LOG2")) slots = (u64)1 << std::max(8, std::min(36, std::atoi(e)));   // (tests: a small set that has to grow, wset_grow)
   while (true) {
     hipError_t e = hipMalloc((void**)&c->h_wset.fp, slots * 8);
     if (e == hipSuccess) e = hipMalloc((void**)&c->h_wset.epoch, slots * 4);
@@ -508,7 +445,7 @@ int32_t vsrmc_checker_create(const vsrmc_model* m, const vsrmc_options* o_in, vs
   for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&c->ev[i]));
   u64 slots = (u64)1 << o->table_log2;
   c->tmask = slots - 1;
-  hipError_t e = table_alloc(&c->table, slots);
+  hipError_t e = hipMalloc((void**)&c->table, slots * sizeof(Slot));
   c->host_frontier = o->host_frontier & 3;
   for (int b = 0; b < 2 && e == hipSuccess; b++) {
     // host_frontier: the records stay in pinned host memory and the kernels read / write them over PCIe (zero-copy); the
@@ -532,15 +469,14 @@ int32_t vsrmc_checker_create(const vsrmc_model* m, const vsrmc_options* o_in, vs
     vsrmc_checker_destroy(c);
     return fail(VSRMC_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
   }
-  c->fused_kernel = (void*)fused_kernel_for(M);
-  c->modes_kernel = (void*)modes_kernel_for(M);
-  c->plain_kernel = (void*)plain_kernel_for(M);
-  c->plain5_kernel = (void*)plain5_kernel_for(M);
-  if (!std::getenv("VSRMC_NO_MODE_KERNELS")) {                   // (A/B knob: the run-time-switched instantiation for every pass, as in rounds 3-4)
-    c->regen_bits_kernel = (void*)one_mode_kernel_for(M, MODE_REGEN);
-    c->insert_kernel = (void*)one_mode_kernel_for(M, MODE_INSERT);
-    c->probe_kernel = (void*)probe_kernel_for(M);
-  }
+  const KernelSet ks = kernels_for(M);
+  c->fused_kernel = (void*)ks.fused;
+  c->modes_kernel = (void*)ks.modes;
+  c->plain_kernel = (void*)ks.plain;
+  c->plain5_kernel = (void*)ks.plain5;
+  c->regen_bits_kernel = (void*)ks.regen_bits;
+  c->insert_kernel = (void*)ks.insert;
+  c->probe_kernel = std::getenv("VSRMC_NO_PROBE_KERNEL") ? nullptr : (void*)ks.probe;   // (tests: the probe passes of the general instantiation)
   rc = checker_seed(c);
   if (rc) { vsrmc_checker_destroy(c); return rc; }
   *out = c;
@@ -682,7 +618,7 @@ int phase_expand(vsrmc_checker* c, const vsrmc_shard_io* io, int mode = MODE_NOR
                          wchunk, tile, ccap, c->filter, c->fmask, c->cand_idx, cchunk,
                          mode | ((mode == MODE_PROBE && (c->saw_violation || c->probe_all_actions)) ? (int)MODE_NO_FOOTPRINT : 0), (u64)0, (const WSet*)nullptr, 0u);
     else
-      hipLaunchKernelGGL(exact_kernel_for(M), dim3(grid), dim3(VSR_BLOCK), lds, c->stream, M, c->words[c->cur], c->off[c->cur],
+      hipLaunchKernelGGL(kernels_for(M).exact, dim3(grid), dim3(VSR_BLOCK), lds, c->stream, M, c->words[c->cur], c->off[c->cur],
                          c->n_frontier, c->level + 1, c->opt.rank, c->table, c->tmask, c->pending, c->opt.pending_entries, c->ctl,
                          c->lds_stride, io ? c->opt.world : 1, io ? io->cand_send : nullptr, io ? io->cand_cap : 0, pchunk, nullptr,
                          0, nullptr, 0, nullptr, 0, 0, tile, ccap, nullptr, 0, io ? c->cand_idx : nullptr, 0, 0, (u64)0, (const WSet*)nullptr, 0u);
@@ -800,7 +736,7 @@ int phase_materialize(vsrmc_checker* c, const u64* entries, u64 n, const uint8_t
   unsigned grid = (unsigned)grid64;
   size_t lds = (size_t)VSR_MAT_BLOCK * c->lds_stride * 8;
   HIPCHK(hipEventRecord(c->ev[2], c->stream));
-  hipLaunchKernelGGL(materialize_kernel_for(M), dim3(grid), dim3(VSR_MAT_BLOCK), lds, c->stream, M, src_words, src_off, entries, n,
+  hipLaunchKernelGGL(kernels_for(M).materialize, dim3(grid), dim3(VSR_MAT_BLOCK), lds, c->stream, M, src_words, src_off, entries, n,
                      c->table, t_words, t_words_cap, t_off, t_cap, t_fp, c->ctl, verdict, cnt_n, cnt_w, c->lds_stride, ichunk, wchunk,
                      entry_words, pidx_arr);
   HIPCHK(hipGetLastError());
@@ -942,9 +878,8 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
   u64 *redo_words = nullptr, *redo_off = nullptr, *redo_fp = nullptr, redo_wcap = 0, redo_cap = 0;
   if (n_parents > 0) {
     // an ordinary level into other buffers (the streamed level's sub-slices) runs the plain instantiation: the code of a stored level
-    static const bool plain_normal = std::getenv("VSRMC_STREAM_MODES_KERNEL") == nullptr;
     const bool one_rank = !io || c->opt.world == 1;                // (world 1 through the level loop: nothing is remote — the unsharded instantiations)
-    const bool use_plain = one_rank && mode == MODE_NORMAL && plain_normal && c->plain_kernel;
+    const bool use_plain = one_rank && mode == MODE_NORMAL && c->plain_kernel;
     FusedShape fs = fused_shape(c, src_max_bag, use_plain);
     // a probe pass (nothing seen to violate so far, no limit re-check): the probe-only instantiation at five blocks per CU when its tile — a work list of 256
     // entries: only the footprint's instances are listed — fits the LDS five times (same measured bound as the five-block ordinary level: fused_shape)
@@ -952,9 +887,8 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
       hipFuncAttributes at;
       const u32 pcap = std::getenv("VSRMC_PROBE_CCAP") ? (u32)std::max(32, std::min(256, std::atoi(std::getenv("VSRMC_PROBE_CCAP")))) : 256u;   // (tests: a list that overflows; 32 = one bag entry per record and batch of the enumeration)
       const size_t dyn = (size_t)64 * fs.stride * 8 + 2 * (size_t)pcap * 4;
-      static const size_t lds5 = std::getenv("VSRMC_LDS5") ? (size_t)std::atoll(std::getenv("VSRMC_LDS5")) : (size_t)31744;
       int nb5 = 0;
-      if (hipFuncGetAttributes(&at, c->probe_kernel) == hipSuccess && dyn + at.sharedSizeBytes <= lds5 &&
+      if (hipFuncGetAttributes(&at, c->probe_kernel) == hipSuccess && dyn + at.sharedSizeBytes <= LDS5_MAX &&
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb5, c->probe_kernel, VSR_BLOCK, dyn) == hipSuccess && nb5 >= VSR_OCC + 1) {
         use_probe = true;
         probe_ccap = pcap;
@@ -988,9 +922,8 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
     grid = (unsigned)std::max<u64>(1, std::min<u64>(grid, d_wcap / (4 * wmin)));
     // index chunks: a block leaves the unused tail of its last chunk behind as invalid refs, and the NEXT pass stages those holes like records.
     // A whole level (2.6e8 states) loses 1-3 % to 8192-index chunks; a sub-slice of a streamed level (7e6 states from 1024 blocks) lost a third
-    // of its index range, and the probe pass over it 16 % of its time (VSRMC_ICHUNK=8192: the old size, for A/B runs).
-    static const u64 ichunk_small = std::getenv("VSRMC_ICHUNK") ? (u64)std::atoll(std::getenv("VSRMC_ICHUNK")) : 2048;
-    const u64 ichunk_max = (dst || mode == MODE_REGEN) ? std::max<u64>(VSR_CAND_CAP, ichunk_small) : 8192;
+    // of its index range, and the probe pass over it 16 % of its time: 2048 for those.
+    const u64 ichunk_max = (dst || mode == MODE_REGEN) ? std::max<u64>(VSR_CAND_CAP, 2048) : 8192;
     const u32 ichunk = (u32)std::max<u64>(VSR_CAND_CAP, std::min<u64>(ichunk_max, nx_cap / (4 * (u64)grid)));
     const u32 wchunk = (u32)std::max<u64>(std::min<u64>(wmin, d_wcap / 2), std::min<u64>(262144, d_wcap / (4 * (u64)grid)));
     HIPCHK(hipEventRecord(c->ev[0], c->stream));

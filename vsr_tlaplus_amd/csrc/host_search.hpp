@@ -293,7 +293,7 @@ static int table_grow(vsrmc_checker* c) {
   if ((double)free_b < (double)new_slots * sizeof(Slot) + 512e6) return 1;
   Slot* nt = nullptr;
   u32* d_err = nullptr;
-  if (table_alloc(&nt, new_slots) != hipSuccess) { (void)hipGetLastError(); return 1; }
+  if (hipMalloc((void**)&nt, new_slots * sizeof(Slot)) != hipSuccess) { (void)hipGetLastError(); return 1; }
   if (hipMalloc((void**)&d_err, 4) != hipSuccess || hipMemsetAsync(d_err, 0, 4, c->stream) != hipSuccess) {
     (void)hipFree(nt);
     if (d_err) (void)hipFree(d_err);

@@ -207,7 +207,7 @@ int deep_run_pass(DeepRun& R, const u64* sw, const u64* so, u64 n, u64 p_off, in
 void deep_claim_bits_alloc(vsrmc_checker* c, u64 src_max_bag) {
   if (c->claim_bits) { (void)hipFree(c->claim_bits); c->claim_bits = nullptr; }
   c->claim_w = c->claim_parents = 0;
-  if (c->opt.world > 1 || !c->regen_bits_kernel || !c->insert_kernel || std::getenv("VSRMC_NO_CLAIM_BITS")) return;   // (two instantiations of k_expand know the bitmap)
+  if (c->opt.world > 1 || !c->regen_bits_kernel || !c->insert_kernel) return;   // (two instantiations of k_expand know the bitmap)
   const Model& M = c->model.M;
   const u64 ords = (u64)M.m0 + std::min<u64>(src_max_bag, (u64)M.max_bag) * (u64)(M.R + 1) + 1;
   const u64 w = (ords + 31) / 32, bytes = c->n_frontier * w * 4;

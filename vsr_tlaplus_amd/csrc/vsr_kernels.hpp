@@ -109,7 +109,7 @@ struct LevelCtl {   // device-resident counters of one BFS level
   u64 cand_cnt[8];         // sharded mode: candidates bucketed for each owner rank
   u64 rec_words;           // words of the records actually written to the next frontier (chunk slack excluded)
   u64 ties;                // fused mode: same-level candidates of one fingerprint with different auxkeys (must stay 0)
-  // shader-clock breakdown (cheap, always on; printed by tools/run_bfs.py).  k_expand, wave 0 of every block: [0..4] stage,
+  // shader-clock breakdown (a -DVSR_PHASE_CLOCKS=1 build only, zero in the product build; printed by tools/run_bfs.py).  k_expand, wave 0 of every block: [0..4] stage,
   // enumerate, sort, apply, tail; fused apply loop of thread 0: [5..7] gen, hash, probe (+ act_generated[0] = successor write);
   // k_materialize (two-kernel levels) adds its lane-0 clocks to [5..7]: fetch + stage, gen + patch, allocate + write
   u64 phase_cycles[8];
@@ -140,8 +140,9 @@ enum { MODE_NORMAL = 0, MODE_PROBE = 1, MODE_INSERT = 2, MODE_REGEN = 3, MODE_NO
 #define VSR_TILE_MAX 128     // frontier records staged per block iteration: 64 or 128 (kernel parameter `tile`)
 #define VSR_BLOCK 256
 // per-phase shader clocks of k_expand (vsrmc_level_info.phase_cycles; tools/run_bfs.py prints the breakdown): every read is an
-// s_memtime that waits for the wave's outstanding LDS / scalar loads.  -DVSR_PHASE_CLOCKS=0 builds without them.
-#ifndef VSR_PHASE_CLOCKS    // round 6: off in the product build (-0.6 %: twelve s_memtime per tile and 16 SGPRs); tools/phase_split.py wants a -DVSR_PHASE_CLOCKS=1 build
+// s_memtime that waits for the wave's outstanding LDS / scalar loads.  Off in the product build (-0.6 %: twelve s_memtime per tile and
+// 16 SGPRs); tools/phase_split.py wants a -DVSR_PHASE_CLOCKS=1 build.
+#ifndef VSR_PHASE_CLOCKS
 #define VSR_PHASE_CLOCKS 0
 #endif
 #if VSR_PHASE_CLOCKS
@@ -150,61 +151,16 @@ enum { MODE_NORMAL = 0, MODE_PROBE = 1, MODE_INSERT = 2, MODE_REGEN = 3, MODE_NO
 #define VSR_CLK() ((u64)0)
 #endif
 #define VSR_CAND_CAP 2048    // enabled instances per tile the LDS work list can hold
-// two-stage enumeration of the enabled instances in k_expand (VSR.tla model): 0 = the full guard for every (record, slot) pair
-// Block barriers of k_expand.  __syncthreads() is "s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier": every barrier also waits until the
-// wave's outstanding GLOBAL stores have been acknowledged — after the apply phase that is the drain of ~28 scattered stores per
-// new state.  Nothing in k_expand hands data from wave to wave through global memory inside a launch (the waves of a block talk
-// through LDS, blocks through atomics), so the barriers only have to order LDS: wait for the wave's LDS operations, then s_barrier.
-// The stores keep draining underneath the next tile's staging loads.
+// Block barriers of k_expand.  Nothing in k_expand hands data from wave to wave through global memory inside a launch: the waves of a
+// block talk through LDS, blocks through atomics.
 // -DVSR_WAVE_DIAG=1 (diagnostic build, tools/wave_diag.py): every wave of k_expand adds up the shader clocks it spends INSIDE the block barriers; the epilogue
 // reports, per wave index 0..3, the barrier time in phase_cycles[0..3] and the wave's whole residency in phase_cycles[4..7] (instead of the phase split).
 // =2: only the barrier that closes the apply loop (the wait for the block's slowest wave of the apply phase) is counted.
 #ifndef VSR_WAVE_DIAG
 #define VSR_WAVE_DIAG 0
 #endif
-#ifndef VSR_TAKE
-#define VSR_TAKE 0
-#endif
-#ifndef VSR_SPEC_CAS
-#define VSR_SPEC_CAS 0
-#endif
-#ifndef VSR_DIRECT_REFS     // every thread fetches the refs of the four records it stages itself (no barrier between the ref load and the record loads)
-#define VSR_DIRECT_REFS 1   // (round 6, with the next switch: config 2 k_expand 130.7 -> 129.5 ms, README 1 091 -> 1 078 ms per step; 0: refs through LDS, as in rounds 1-5)
-#endif
-#ifndef VSR_NO_TAIL_SYNC    // no barrier at the bottom of the tile loop (what follows the apply-closing barrier touches LDS words of wave 0 only)
-#define VSR_NO_TAIL_SYNC 1
-#endif
-#ifndef VSR_COPY8
-#define VSR_COPY8 0
-#endif
-#ifndef VSR_TILE128         // EXPERIMENT: tiles of 128 records (three blocks per CU) for the ordinary levels of the specialised instantiations too: the fixed cost per tile over twice the records
-#define VSR_TILE128 0
-#endif
-#ifndef VSR_TAKE_BATCH      // -DVSR_TAKE: records per draw from the cursor
-#define VSR_TAKE_BATCH 512
-#endif
-#ifndef VSR_TILE_BATCH      // tiles a block draws from the cursor at a time (k_expand: s_tile_left); 1 = rounds 1-5
-#define VSR_TILE_BATCH 4
-#endif
-#ifndef VSR_REDO            // a tile that overflows the work list is taken again in pieces (k_expand: s_redo_*); 0: ERR_FRONTIER_FULL as in rounds 1-5 (A/B; the experiments below need 0)
-#define VSR_REDO 1
-#endif
-#ifndef VSR_REFS_AHEAD
-#define VSR_REFS_AHEAD 0
-#endif
-#if (VSR_REFS_AHEAD || VSR_TAKE) && VSR_REDO
-#undef VSR_REDO
-#define VSR_REDO 0
-#endif
-#ifndef VSR_COOP_COPY       // wave-cooperative copy of the parent words of new states in the ordinary level's instantiation (see the apply loop); 0: the lane-serial copy everywhere
-#define VSR_COOP_COPY 1
-#endif
-
-#ifndef VSR_ROUND_REV       // EXPERIMENT: the second round of the apply loop runs on the block's LAST waves (wave 0 carries the serial sections already)
-#define VSR_ROUND_REV 0
-#endif
-// =3: wave 1's waits per barrier GROUP (0 top / bottom of the tile loop, 1 after the ref load, 2 after staging, 3 after the work-list fill + parent fingerprints,
-// 4 inside the enumeration, 5 after it, 6 sort / reservations, 7 the barrier that closes the apply loop) in phase_cycles[0..7], its residency in act_generated[0].
+// =3: wave 1's waits per barrier GROUP (0 top of the tile loop, 2 after staging, 3 after the work-list fill + parent fingerprints, 4 inside the
+// enumeration, 5 after it, 6 sort / reservations, 7 the barrier that closes the apply loop; group 1 has no barrier) in phase_cycles[0..7], its residency in act_generated[0].
 #if VSR_WAVE_DIAG == 3
 #define VSR_SYNC_G(g) do { const u64 b0_ = __builtin_readcyclecounter(); __syncthreads(); if (tid == 64) s_wd[g] += __builtin_readcyclecounter() - b0_; } while (0)
 #elif VSR_WAVE_DIAG
@@ -212,16 +168,11 @@ enum { MODE_NORMAL = 0, MODE_PROBE = 1, MODE_INSERT = 2, MODE_REGEN = 3, MODE_NO
 #else
 #define VSR_SYNC_G(g) __syncthreads()
 #endif
-// seen-set probes read the home slot (16 B) first and the rest of its 64-byte line only when that slot holds another fingerprint
-// successor write: parent words copied eight per trip (four LDS reads in flight) instead of two
-// intra-tile duplicate filter in LDS ahead of the seen-set probes of k_expand (single-pass levels)
-#ifndef VSR_OCC            // resident blocks per CU the specialised fused kernels are compiled for (4 = 128 VGPRs; 5 = 96: experiment)
-#define VSR_OCC 4
-#endif
-#ifndef VSR_PROBE_FOOTPRINT   // probe level: only the actions that write what the invariants read are applied (Ops::probe_actions)
-#define VSR_PROBE_FOOTPRINT 1
-#endif
-// frontier refs of a tile are loaded one tile ahead (tiles are drawn two ahead): the staging of a tile starts with its record loads
+// Tiles a block draws from the cursor at a time (k_expand: s_tile_left).
+constexpr int VSR_TILE_BATCH = 4;
+// Resident blocks per CU the specialised fused kernels are compiled for (4 = 128 VGPRs); the five-block instantiations (EXPAND_PLAIN5,
+// EXPAND_PROBE) are compiled for one more.
+constexpr int VSR_OCC = 4;
 
 __device__ __forceinline__ void raise_error(LevelCtl* ctl, int code, u64 info) {
   if (atomicCAS(&ctl->err, 0u, (u32)code) == 0u) ctl->err_info = info;
@@ -296,7 +247,8 @@ __device__ __forceinline__ u64 wave_alloc(u64* counter) {
   return base + (u64)__popcll(active & (((u64)1 << lane) - 1));
 }
 
-// Find-or-insert of a fingerprint: linear probing from fp & mask, one 64-byte line (4 slots) per memory round trip.
+// Find-or-insert of a fingerprint: linear probing from fp & mask, one 64-byte line (4 slots) per memory round trip.  The home slot (16 B)
+// is read first, the rest of its line only when that slot holds another fingerprint.
 // A loaded line may be stale with respect to concurrent inserts, which is harmless: a slot only ever goes empty -> fp and
 // never changes afterwards, so "other key" and "this key" are final, and "empty" is re-checked by the atomicCAS.
 // how a probe sequence is counted (vsrmc_level_info.probes, informational): in a register of the lane (small kernels), or — in k_expand, where
@@ -325,22 +277,6 @@ __device__ __forceinline__ Probe probe_insert(Slot* table, u64 mask, u64 fp, CNT
   Probe r;
   r.slot = 0; r.meta = META_EMPTY; r.claimed = false; r.reload = false; r.full = false;
   u64 i = fp & mask;
-#if VSR_SPEC_CAS
-  // EXPERIMENT: the compare-and-swap of the home slot is issued TOGETHER with its 16-byte load (a new state then costs one memory round trip, not two
-  // dependent ones); an occupied slot makes the atomic a no-op that returns what the slot holds
-  {
-    const u64 old = atomicCAS((unsigned long long*)&table[i].fp, 0ull, (unsigned long long)fp);
-    const u64x2 sk = *(const u64x2*)&table[i];
-    nprobe.home();
-    if (old == 0) { r.slot = i; r.claimed = true; return r; }
-    if (old == fp) {
-      r.slot = i;
-      if (sk.x == fp) r.meta = sk.y; else r.reload = true;
-      return r;
-    }
-    i = (i + 1) & mask;
-  }
-#else
   {
     const u64x2 sk = *(const u64x2*)&table[i];
     nprobe.home();
@@ -356,7 +292,6 @@ __device__ __forceinline__ Probe probe_insert(Slot* table, u64 mask, u64 fp, CNT
     }
     i = (i + 1) & mask;
   }
-#endif
   for (u32 lines = 0; lines < 2048; lines++) {
     const u64 lb = i & ~(u64)3;
     const u64x2* lp = (const u64x2*)&table[lb];
@@ -509,17 +444,28 @@ __device__ __forceinline__ void specialise(Model& M, const Model& Marg) {
 // in the constants, still specific to the model): the constants of the model
 // become compile-time constants of this instantiation (every device function below is inlined), so loops over replicas,
 // clients, values and permutations unroll without predicates and strides fold into addresses.
-// BLK = threads per block = 256: four waves share a tile of 64 (or 128) records, block barriers between the phases.  (One wave per block
+// VSR_BLOCK = threads per block = 256: four waves share a tile of 64 (or 128) records, block barriers between the phases.  (One wave per block
 // with a 16-record tile of its own and 512-thread blocks were built and measured in round 3: 268 and 212 ms against 156 — DESIGN.md §5.)
+// PLAIN: what a single-pass instantiation (FUSED) compiles in.  A pass that knows its mode runs leaner code: the instantiation that carries every mode
+// behind a run-time switch pays for it in registers (its README build spills 27 VGPRs; one more branch took that to 93, and every pass 10 % with it).
+constexpr int EXPAND_GENERAL = 0;      // every mode, sharded or not
+constexpr int EXPAND_PLAIN = 1;        // the unsharded, ordinary level: the modes and the sharded branches are compiled out (11 % less code: the
+                                       // specialised kernel then fits the 64-KB instruction cache with room to spare)
+constexpr int EXPAND_MODES = 2;        // unsharded with the modes (the probe / virtual / regenerated / streamed passes of vsrmc_checker_probe*): only the
+                                       // sharded branches are compiled out — the README configuration's kernel then fits the 64-KB instruction cache
+constexpr int EXPAND_REGEN_BITS = 3;   // unsharded, MODE_REGEN by the claim bitmap only: no guards and no seen-set code at all
+constexpr int EXPAND_INSERT = 4;       // unsharded, MODE_INSERT only (a virtual level: no successor write; leaves the claim bitmap)
+constexpr int EXPAND_PLAIN5 = 5;       // EXPAND_PLAIN compiled for five blocks per CU
+constexpr int EXPAND_PROBE = 6;        // the PROBE pass of the deep search and nothing else, five blocks per CU (see k_expand)
 // Resident blocks per CU an instantiation is compiled for (= its register budget: 4 -> 128 VGPRs, 5 -> 96).  Round 6: with MachineLICM off (build.py) the
 // ordinary level's kernel of BASELINE configs[1] needs 107 registers and runs FIVE blocks per CU with 7 spilled ones at the top of the tile loop (k_expand
 // 139 -> 134.6 ms; with the cooperative copy 127.9); the README configuration's (six permutations: 119 registers) loses at five (28 spilled: 232 -> 257 ms).
 constexpr int expand_occ(bool fused, int spec, int plain) {
-  return !fused ? 3 : spec == 0 ? 2 : (plain == 5 || plain == 6) ? VSR_OCC + 1 : VSR_OCC;
+  return !fused ? 3 : spec == 0 ? 2 : (plain == EXPAND_PLAIN5 || plain == EXPAND_PROBE) ? VSR_OCC + 1 : VSR_OCC;
 }
-template <bool FUSED, int SPEC = 0, int PLAIN = 0, int BLK = VSR_BLOCK>
+template <bool FUSED, int SPEC = 0, int PLAIN = EXPAND_GENERAL>
 // (hipcc turns the second bound into waves per SIMD as blocks * max(1, threads / 256): 4 = 128 VGPRs)
-__global__ void __launch_bounds__(BLK, expand_occ(FUSED, SPEC, PLAIN) / (BLK > VSR_BLOCK ? BLK / VSR_BLOCK : 1))
+__global__ void __launch_bounds__(VSR_BLOCK, expand_occ(FUSED, SPEC, PLAIN))
 k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ fr_off, u64 n_parents, int level, int rank,
          Slot* table, u64 tmask, u64* pending, u64 pending_cap, LevelCtl* ctl, int stride, int world_arg, u64* cand_send,
          u64 cand_cap, u32 pchunk /* pending entries a block reserves per global atomic, >= ccap */,
@@ -542,25 +488,18 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
          // sharded deep search (world > 1, a pass beyond the record buffers): the rank's winner set — MODE_INSERT / MODE_NORMAL record the states this
          // rank's own lanes insert, MODE_REGEN rebuilds exactly the states the set holds, once per descent (wepoch), and announces nothing
          const WSet* wset, u32 wepoch) {
-  // PLAIN: the unsharded, ordinary level — the probe / virtual-level modes and the sharded branches are compiled out (11 % less
-  // code: the specialised kernel then fits the 64-KB instruction cache with room to spare)
-  // PLAIN == 2: unsharded with the modes (the probe / virtual / regenerated / streamed passes of vsrmc_checker_probe*): only the
-  // sharded branches are compiled out — the mode-capable kernel of the README configuration then fits the 64-KB instruction cache
-  // PLAIN == 3 / 4 (round 5): unsharded with ONE mode compiled in — 3 = MODE_REGEN by the claim bitmap (no guards and no seen-set code at all), 4 =
-  // MODE_INSERT (a virtual level: no successor write; leaves the claim bitmap).  The mode-capable instantiation carries every mode behind a run-time switch
-  // and pays for it in registers (its README build spills 27 VGPRs; one more branch took that to 93, and every pass 10 % with it): a pass that knows its mode
-  // runs leaner code.  (A probe-only instantiation was built too and lost to the run-time-switched one — 88 spilled VGPRs: DESIGN.md §8.5.)
-  constexpr bool IS_PLAIN = PLAIN == 1 || PLAIN == 5;          // the ordinary level's instantiation (5: the same compiled for five blocks per CU)
-  // PLAIN == 6 (round 6): the PROBE pass of the deep search and nothing else, compiled for FIVE blocks per CU.  A probe pass stages and enumerates every
-  // parent but applies 2 % of the instances (the actions inside the invariants' footprint) and fingerprints only a successor that FAILS an invariant — 8 of
-  // 3.8e9 on the README configuration.  Here that rare successor is not fingerprinted at all: its (parent, ordinal) goes to the `pending` list and a small
-  // kernel of its own (k_probe_resolve) hashes it and looks it up after the pass; and the instances outside the footprint are counted, not listed.  Without
-  // the hash of six permutations and the seen-set code the kernel fits 96 registers, and with a work list of 256 entries its tile fits the LDS five times.
-  const int mode = IS_PLAIN ? (int)MODE_NORMAL : PLAIN == 3 ? (int)MODE_REGEN : PLAIN == 4 ? (int)MODE_INSERT : PLAIN == 6 ? (int)MODE_PROBE : (mode_arg & 0xFF);
+  constexpr bool IS_PLAIN = PLAIN == EXPAND_PLAIN || PLAIN == EXPAND_PLAIN5;   // the ordinary level's instantiations
+  // EXPAND_PROBE: a probe pass stages and enumerates every parent but applies 2 % of the instances (the actions inside the invariants' footprint) and
+  // fingerprints only a successor that FAILS an invariant — 8 of 3.8e9 on the README configuration.  Here that rare successor is not fingerprinted at all:
+  // its (parent, ordinal) goes to the `pending` list and a small kernel of its own (k_probe_resolve) hashes it and looks it up after the pass; and the
+  // instances outside the footprint are counted, not listed.  Without the hash of six permutations and the seen-set code the kernel fits 96 registers, and
+  // with a work list of 256 entries its tile fits the LDS five times.
+  const int mode = IS_PLAIN ? (int)MODE_NORMAL : PLAIN == EXPAND_REGEN_BITS ? (int)MODE_REGEN : PLAIN == EXPAND_INSERT ? (int)MODE_INSERT
+                 : PLAIN == EXPAND_PROBE ? (int)MODE_PROBE : (mode_arg & 0xFF);
   // MODE_NO_FOOTPRINT: the probe pass applies every action — the caller has seen a violating state among the parents' levels (a search that
   // went on after a reported violation), and a violating parent hands its verdict to successors of actions outside the footprint
-  const bool no_footprint = !IS_PLAIN && PLAIN != 6 && (mode_arg & MODE_NO_FOOTPRINT) != 0;
-  const int world = PLAIN ? 1 : world_arg;
+  const bool no_footprint = !IS_PLAIN && PLAIN != EXPAND_PROBE && (mode_arg & MODE_NO_FOOTPRINT) != 0;
+  const int world = PLAIN != EXPAND_GENERAL ? 1 : world_arg;
   Model M = Marg;
   specialise<SPEC>(M, Marg);
   typedef ModelOps<SPEC / 1000> Ops;
@@ -570,9 +509,9 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
   u32* s_cand2 = s_cand + ccap;                        // the same, sorted by action
   __shared__ u32 s_ncand, s_napply, s_dead, s_maxbag, s_maxbag_out, s_skip, s_nsurv, s_risky, s_ntotal;
   // (single-pass levels of a configuration with R <= 3 always run 64-record tiles: host_checker.hpp, fused_shape — 1.3 KB of LDS less, which five blocks per CU need)
-  constexpr int TILE_MAX = BLK < VSR_BLOCK ? BLK / 2 : (!VSR_TILE128 && FUSED && SPEC % 1000 != 0 && (SPEC % 1000) / 100 <= 3) ? 64 : VSR_TILE_MAX;
-  constexpr bool COOP = VSR_COOP_COPY && FUSED && IS_PLAIN;
-  constexpr bool REDO_OK = VSR_REDO && FUSED && (IS_PLAIN || PLAIN == 6);   // a tile that overflows the work list goes to the host's list (LevelCtl::n_redo) instead of failing the launch
+  constexpr int TILE_MAX = (FUSED && SPEC % 1000 != 0 && (SPEC % 1000) / 100 <= 3) ? 64 : VSR_TILE_MAX;
+  constexpr bool COOP = FUSED && IS_PLAIN;                     // wave-cooperative copy of the parent words of new states (see the apply loop)
+  constexpr bool REDO_OK = FUSED && (IS_PLAIN || PLAIN == EXPAND_PROBE);   // a tile that overflows the work list goes to the host's list (LevelCtl::n_redo) instead of failing the launch
   __shared__ u32 s_alive[TILE_MAX];
   __shared__ u64 s_ref[TILE_MAX];
   __shared__ u64 s_pfp[TILE_MAX];                          // canonical fingerprint of every staged record (the parent part of its successors' keys)
@@ -621,44 +560,12 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
   // min-merged predecessor keys do not depend on it.
   __shared__ u64 s_tile_cur;
   u64 my_next = 0;
-#if VSR_TAKE
-  // EXPERIMENT (-DVSR_TAKE=<candidates>): the apply loop runs in rounds of BLK lanes and a tile of 64 records yields 320 (config 2) .. 416 (README)
-  // instances: the second round is a quarter / two thirds full and three waves wait for the one that runs it.  Here a tile is as many RECORDS as are
-  // expected to yield VSR_TAKE instances (smoothed instances per record of the block's own tiles); the cursor counts records, not tiles.
-  __shared__ u32 s_tile_n;
-  u32 my_take = (u32)tile, my_n = 0, avg_q8 = 0;                // thread 0: records to draw next time / drawn with my_next / instances per record x 256
-  // (the cursor is drawn VSR_TAKE_BATCH records at a time — see VSR_TILE_BATCH below — and the block cuts its batch into tiles)
-  __shared__ u64 s_take_end;                                     // end of the drawn batch (thread 0's)
-  if (tid == 0) {
-    my_next = atomicAdd((unsigned long long*)&ctl->tile_cursor, (unsigned long long)VSR_TAKE_BATCH);
-    s_take_end = my_next + VSR_TAKE_BATCH;
-    my_n = my_take;
-  }
-#elif VSR_REFS_AHEAD
-  // EXPERIMENT: the refs of a tile are fetched while the tile BEFORE it is staged (tiles are drawn two ahead), so staging starts with the record loads —
-  // one HBM round trip per tile instead of two dependent ones
-  __shared__ u64 s_tile_nxt;
-  __shared__ u64 s_ref2[TILE_MAX];
-  u64 my_next2 = 0;
-  if (tid == 0) {
-    my_next = atomicAdd((unsigned long long*)&ctl->tile_cursor, 1ull);
-    my_next2 = atomicAdd((unsigned long long*)&ctl->tile_cursor, 1ull);
-    s_tile_nxt = my_next;
-  }
-  VSR_SYNC_G(0);
-  if (tid < tile) {
-    const u64 i0 = s_tile_nxt * (u64)tile + (u64)tid;
-    s_ref2[tid] = (s_tile_nxt < ntiles && i0 < n_parents) ? fr_off[i0] : 0;
-  }
-  VSR_SYNC_G(0);                                                // (thread 0 rewrites s_tile_nxt at the top of the loop)
-#else
   // Round 6: VSR_TILE_BATCH consecutive tiles per draw.  Atomics on ONE address are served one after the other — 13 - 15 ns each on this part (the staging
   // micro-benchmark: 65 - 75 tiles per microsecond whatever the layout, the occupancy or the prefetch depth, tools/bench_layout.py) — and a pass that only
   // stages and enumerates (the probe pass: 65 tiles per microsecond) ran AT that rate: the cursor, not the HBM, was its bound.
   __shared__ u32 s_tile_left;                                    // tiles left of the drawn batch after my_next (thread 0's)
   const u32 tbatch = ntiles >= (u64)gridDim.x * 16 ? (u32)VSR_TILE_BATCH : 1u;   // (the same in every block of the launch; a small level keeps single tiles: every block gets work)
   if (tid == 0) { my_next = atomicAdd((unsigned long long*)&ctl->tile_cursor, 1ull) * (u64)tbatch; s_tile_left = tbatch - 1; }
-#endif
   // A tile whose enabled instances do not fit the work list (ccap entries: 12 .. 24 per record, the mean is 5 - 7) is not an error for the ordinary level's
   // instantiations since round 6: nothing of it has been applied when the counting sort finds out, so the block writes the tile down (its first record and
   // its size, in the `pending` list an ordinary single-pass level has no other use for) and goes on; the host launches the listed tiles again in halves
@@ -669,28 +576,11 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
   for (;;) {
     if (tid == 0) {
       s_tile_cur = my_next;
-#if VSR_REFS_AHEAD
-      s_tile_nxt = my_next2;
-      my_next = my_next2;
-      if (my_next2 < ntiles) my_next2 = atomicAdd((unsigned long long*)&ctl->tile_cursor, 1ull);
-    }
-    if (0) {
-#endif
-#if VSR_TAKE
-      s_tile_n = my_n;
-      if (my_next < n_parents) {
-        const u64 end = s_take_end;
-        my_next += my_n;
-        if (my_next >= end) { my_next = atomicAdd((unsigned long long*)&ctl->tile_cursor, (unsigned long long)VSR_TAKE_BATCH); s_take_end = my_next + VSR_TAKE_BATCH; my_n = my_take; }
-        else { const u64 room = end - my_next; my_n = (room < (u64)my_take + 8 && room <= (u64)tile) ? (u32)room : my_take; }   // (a remainder of fewer than 8 records rides with the last tile)
-      }
-#else
       if (my_next < ntiles) {
         const u32 left = s_tile_left;
         if (left) { my_next++; s_tile_left = left - 1; }
         else { my_next = atomicAdd((unsigned long long*)&ctl->tile_cursor, 1ull) * (u64)tbatch; s_tile_left = tbatch - 1; }
       }
-#endif
     }
     const u64 t_0 = VSR_CLK();
     if (tid == 0) { s_ncand = 0; s_dead = 0; s_maxbag = 0; s_wneed = 0; s_skip = 0; s_nsurv = 0; s_over = 0; if (!IS_PLAIN) s_risky = 0; }
@@ -699,11 +589,6 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
     VSR_SYNC_G(0);
     u64 tile_i = s_tile_cur;
     tile_i = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(tile_i >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)tile_i);   // (block-uniform: scalar)
-#if VSR_TAKE
-    if (tile_i >= n_parents) break;
-    const u64 p_base = tile_i;
-    const int np_tile = (int)((n_parents - p_base) < (u64)s_tile_n ? (n_parents - p_base) : (u64)s_tile_n);
-#else
     if (tile_i >= ntiles) break;
     u64 p_base = tile_i * (u64)tile;
     int np_tile = (int)((n_parents - p_base) < (u64)tile ? (n_parents - p_base) : (u64)tile);
@@ -722,13 +607,12 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       p_base = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(p_base >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)p_base);
       np_tile = __builtin_amdgcn_readfirstlane(np_tile);
     }
-#endif
-    // PLAIN == 3 (regeneration by the claim bitmap): the bitmap IS the list of enabled instances that matter — the (parent, ordinal) pairs whose lane
+    // PLAIN == EXPAND_REGEN_BITS (regeneration by the claim bitmap): the bitmap IS the list of enabled instances that matter — the (parent, ordinal) pairs whose lane
     // made a state when the level was inserted.  The words of this thread's record (thread g of the record's G threads takes words g and g + G; the host
     // offers the bitmap only when 2 G words cover a parent) are fetched now, so that their latency hides behind the staging loads.
     u32 cbits[2] = {0u, 0u};
-    if constexpr (PLAIN == 3) {
-      const int pm = tid & (tile - 1), gg = tid >> tshift, GG = BLK >> tshift;
+    if constexpr (PLAIN == EXPAND_REGEN_BITS) {
+      const int pm = tid & (tile - 1), gg = tid >> tshift, GG = VSR_BLOCK >> tshift;
       if (pm < np_tile) {
         const u32* row = (const u32*)filter + (p_offset + p_base + (u64)pm) * fmask;
 #pragma unroll
@@ -737,48 +621,29 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       }
     }
 
-    // ---- stage the tile.  Frontier refs are (word offset << 8 | length): one coalesced load of 64 refs, then 16 lanes per
-    // record / 16 records per pass, all 16 loads of a thread issued before the first LDS store (one HBM latency per tile)
-#if VSR_REFS_AHEAD
-    u64 ref_pre = 0;                                            // wave 0: the refs of the NEXT tile, on their way while this one is staged
-    if (tid < tile) {
-      const u64 i1 = s_tile_nxt * (u64)tile + (u64)tid;
-      if (s_tile_nxt < ntiles && i1 < n_parents) ref_pre = fr_off[i1];
-    }
-#endif
+    // ---- stage the tile.  Frontier refs are (word offset << 8 | length).  The first np_tile threads keep one ref each in LDS (s_ref, for the
+    // later phases), and every thread fetches the refs of the four records it stages itself, so that no barrier stands between the ref loads
+    // and the record loads (round 6, with no barrier at the bottom of the tile loop: config 2 k_expand 130.7 -> 129.5 ms); 16 lanes per record /
+    // 16 records per pass, all 16 loads of a thread issued before the first LDS store
     if (tid < np_tile) {
-#if VSR_REFS_AHEAD
-      const u64 ref = s_ref2[tid];
-#else
       const u64 ref = fr_off[p_base + tid];
-#endif
       s_ref[tid] = ref;
       if (ref) atomicMax(&s_maxbag, (u32)((int)(ref & 255) - M.fixed));
       if ((int)(ref & 255) > stride) raise_error(ctl, ERR_INTERNAL, (p_base + (u64)tid) << 16);   // LDS slots sized for shorter records
     }
-#if !VSR_DIRECT_REFS
-    VSR_SYNC_G(1);
-#endif
-    constexpr int SG = BLK / 16;                                 // records staged per pass (16 lanes each)
+    constexpr int SG = VSR_BLOCK / 16;                           // records staged per pass (16 lanes each)
     for (int half = 0; half < tile; half += 4 * SG)
       for (int wbase = 0; wbase < stride; wbase += 64) {      // records longer than 64 words (R >= 4): a second window
         u64 v[4][4];
-#if VSR_DIRECT_REFS
         u64 refq[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           const int p = half + (tid >> 4) + SG * q;
           refq[q] = p < np_tile ? fr_off[p_base + (u64)p] : 0;
         }
-#endif
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-          const int p = half + (tid >> 4) + SG * q;
-#if VSR_DIRECT_REFS
           const u64 ref = refq[q];
-#else
-          const u64 ref = p < np_tile ? s_ref[p] : 0;
-#endif
           const u64 off = ref >> 8;
           const int len = (int)(ref & 255) < stride ? (int)(ref & 255) : stride;
 #pragma unroll
@@ -790,11 +655,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           const int p = half + (tid >> 4) + SG * q;
-#if VSR_DIRECT_REFS
           const int len = (int)(refq[q] & 255) < stride ? (int)(refq[q] & 255) : stride;
-#else
-          const int len = p < np_tile ? ((int)(s_ref[p] & 255) < stride ? (int)(s_ref[p] & 255) : stride) : 0;
-#endif
 #pragma unroll
           for (int j = 0; j < 4; j++) {
             const int k = wbase + (tid & 15) + 16 * j;
@@ -802,9 +663,6 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           }
         }
       }
-#if VSR_REFS_AHEAD
-    if (tid < tile) s_ref2[tid] = ref_pre;                      // (read again at the top of the next tile, two barriers from here)
-#endif
     VSR_SYNC_G(2);
     if (tid < np_tile && s_ref[tid] != 0) {                     // the parent's own fingerprint, from the view hashes it carries
       const u64* r0 = s_rec + tid * stride;
@@ -838,9 +696,9 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       // in a register, no atomics, no cross-lane traffic inside the slot loop; the entries beyond 256*PRIV are a shared
       // overflow area (atomic cursor) for the rare thread that finds more.  Unused entries hold ~0; the counting sort below
       // skips them.
-      const u32 PRIV = PLAIN == 6 ? 0u : (ccap - (u32)BLK) / BLK;   // 5 at ccap 1536, 7 at 2048; the probe-only instantiation lists 2 % of the instances: one shared region
-      const u32 shared0 = PRIV * BLK;
-      for (u32 k = tid; k < ccap; k += BLK) s_cand[k] = ~0u;
+      const u32 PRIV = PLAIN == EXPAND_PROBE ? 0u : (ccap - (u32)VSR_BLOCK) / VSR_BLOCK;   // 5 at ccap 1536, 7 at 2048; the probe-only instantiation lists 2 % of the instances: one shared region
+      const u32 shared0 = PRIV * VSR_BLOCK;
+      for (u32 k = tid; k < ccap; k += VSR_BLOCK) s_cand[k] = ~0u;
       VSR_SYNC_G(3);
       u32 nmine = 0;
       bool alive = false;
@@ -852,7 +710,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         // instances of a record are evaluated as one bit mask per replica by the record's threads (thread g takes replicas g+1, g+1+G, ..).
         auto emit = [&](int kind, int p, int ord) {
           atomicAdd(&s_kcount[kind], 1u);
-          if constexpr (PLAIN == 6) {                               // the probe-only instantiation lists what it will apply; the rest is counted
+          if constexpr (PLAIN == EXPAND_PROBE) {                               // the probe-only instantiation lists what it will apply; the rest is counted
             if (!((Ops::probe_actions() >> kind) & 1u)) { s_alive[p] = 1; return; }
           }
           u32 idx;
@@ -863,8 +721,8 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           else s_ncand = 0x40000000u;                             // overflow marker (work list too small)
           s_alive[p] = 1;
         };
-        const int G = BLK >> tshift, g = tid >> tshift;     // threads per record, this thread's rank among them
-        if constexpr (PLAIN == 3) {
+        const int G = VSR_BLOCK >> tshift, g = tid >> tshift;     // threads per record, this thread's rank among them
+        if constexpr (PLAIN == EXPAND_REGEN_BITS) {
           // no guards, no bag scans: every set bit is an instance that was enabled (and made a state) when the level was inserted; only its action id has
           // to be found again — by the ordinal's range, or, for a message-bound one, by the one slot's own guard (which also names the action)
           if (mine_valid) {
@@ -918,7 +776,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
               const int r = m_dest(w);
               const u64 l = r == 1 ? lut[1] : r == 2 ? lut[2] : r == 3 ? lut[3] : r == 4 ? lut[4] : lut[5];
               pass = m_count(w) != 0 && ((l >> (w & 63)) & 1);
-              if (!IS_PLAIN && PLAIN != 3 && PLAIN != 4 && mode == MODE_PROBE && m_count(w) == 3) s_risky = 1;   // one more Send of this key would not fit the count field
+              if (!IS_PLAIN && PLAIN != EXPAND_REGEN_BITS && PLAIN != EXPAND_INSERT && mode == MODE_PROBE && m_count(w) == 3) s_risky = 1;   // one more Send of this key would not fit the count field
             }
             const u64 bal = __ballot(pass);
             if (bal) {
@@ -930,7 +788,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           }
           VSR_SYNC_G(4);
           const u32 nsurv = s_nsurv;
-          for (u32 i = tid; i < nsurv; i += BLK) {
+          for (u32 i = tid; i < nsurv; i += VSR_BLOCK) {
             const int p = s_surv[i] >> 8, j = s_surv[i] & 255;
             int kind0 = 0;
             u32 mask = Ops::guard(M, s_rec + p * stride, M.m0 + j, &kind0);
@@ -947,16 +805,16 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
             VSR_SYNC_G(4);
           }
         }
-        }   // (PLAIN != 3)
+        }   // (PLAIN != EXPAND_REGEN_BITS)
       } else
       {
       // four independent guard evaluations per trip
-      for (int item0 = tid; item0 < nitems; item0 += 4 * BLK) {
+      for (int item0 = tid; item0 < nitems; item0 += 4 * VSR_BLOCK) {
         u32 masks[4];
         int kinds[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-          const int item = item0 + u * BLK;
+          const int item = item0 + u * VSR_BLOCK;
           const int slot = item >> tshift;
           masks[u] = 0;
           kinds[u] = 0;
@@ -966,7 +824,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         for (int u = 0; u < 4; u++) {
           u32 mask = masks[u];
           if (!mask) continue;
-          const int slot = (item0 + u * BLK) >> tshift;
+          const int slot = (item0 + u * VSR_BLOCK) >> tshift;
           const int ordbase = slot < M.m0 ? slot : M.m0 + (slot - M.m0) * (M.R + 1);
           alive = true;
           while (mask) {
@@ -1006,7 +864,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       // its instances are counted and sorted behind the others, and the apply loop stops in front of them.  (Compiled into the mode-capable
       // kernels only: the plain kernels sit on a register-allocation cliff — one more LDS word here cost the README configuration's 20
       // stored levels 22 ms.)
-      if constexpr (!IS_PLAIN && FUSED && VSR_PROBE_FOOTPRINT) {
+      if constexpr (!IS_PLAIN && FUSED) {
         const u32 keep = (mode == MODE_PROBE && !no_footprint) ? Ops::probe_actions() : ~0u;
         for (int a = 0; a < 16; a++)
           if ((keep >> a) & 1u) {
@@ -1030,15 +888,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         }
       }
       s_ncand = acc > ccap ? ccap : acc;
-      if constexpr (PLAIN == 6) { s_ntotal = acc; s_ncand = s_napply; }   // (listed = the footprint's instances; every instance counts as generated)
-#if VSR_TAKE
-      {
-        const u32 q8 = (acc << 8) / (u32)np_tile;
-        avg_q8 = avg_q8 ? (3u * avg_q8 + q8) >> 2 : q8;
-        const u32 want = avg_q8 ? ((u32)VSR_TAKE << 8) / avg_q8 : (u32)tile;
-        my_take = want < 8u ? 8u : want > (u32)tile ? (u32)tile : want;
-      }
-#endif
+      if constexpr (PLAIN == EXPAND_PROBE) { s_ntotal = acc; s_ncand = s_napply; }   // (listed = the footprint's instances; every instance counts as generated)
       if (fused) s_wneed = s_ncand * (u32)(M.fixed + (int)s_maxbag + 5);   // upper bound of the successors' total length
     }
     const u64 t_2 = VSR_CLK();
@@ -1050,7 +900,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         continue;
       }
     }
-    for (u32 c = tid; c < ccap; c += BLK) {
+    for (u32 c = tid; c < ccap; c += VSR_BLOCK) {
       const u32 code = s_cand[c];
       if (code == ~0u) continue;
       const u32 pos = atomicAdd(&s_kbase[code >> 18], 1u);
@@ -1064,7 +914,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       if (s_ich_used + ncand > ichunk) {                        // block-uniform
         const u32 used = s_ich_used;
         const u64 base = s_ich_base;
-        for (u32 k = used + tid; k < ichunk; k += BLK) {  // unused indices of the old chunk: invalid refs
+        for (u32 k = used + tid; k < ichunk; k += VSR_BLOCK) {  // unused indices of the old chunk: invalid refs
           nx_off[base + k] = 0;
           lvl_fp[base + k] = 0;
         }
@@ -1096,7 +946,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
     if (!fused && s_chunk_used + ncand > pchunk) {          // block-uniform
       const u32 used = s_chunk_used;
       const u64 base = s_chunk_base;
-      for (u32 k = used + tid; k < pchunk && used < pchunk; k += BLK) pending[3 * (base + k) + 1] = ~(u64)0;
+      for (u32 k = used + tid; k < pchunk && used < pchunk; k += VSR_BLOCK) pending[3 * (base + k) + 1] = ~(u64)0;
       VSR_SYNC_G(6);
       if (tid == 0) {
         u64 nb = atomicAdd((unsigned long long*)&ctl->n_pending, (unsigned long long)pchunk);
@@ -1109,8 +959,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       }
       VSR_SYNC_G(6);
     }
-    const u32 ncand_apply = s_skip ? 0u : ((!IS_PLAIN && FUSED && VSR_PROBE_FOOTPRINT) ? s_napply : ncand);                // s_skip: the tile was refused (see the word-chunk reservation)
-    constexpr bool dd_on = false;
+    const u32 ncand_apply = s_skip ? 0u : ((!IS_PLAIN && FUSED) ? s_napply : ncand);                // s_skip: the tile was refused (see the word-chunk reservation)
     if (tid == 0) { s_tile_base = s_chunk_used; s_tile_cursor = 0; }
     VSR_SYNC_G(6);
     // ---- apply + fingerprint + seen-set claim: one lane per enabled instance
@@ -1118,13 +967,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
     // written come from the tile's word cursor, the largest bag / the virtual level's checksums go to LDS when a state is new, probes are counted
     // as one per candidate plus an LDS atomic per slot beyond the home slot)
     const CntLds my_probes{&s_acc[2]};
-#if VSR_ROUND_REV
-    for (u32 c0 = 0; c0 < ncand_apply; c0 += BLK) {
-      const u32 c = c0 + (((c0 / BLK) & 1u) ? (u32)(BLK - 1 - tid) : (u32)tid);
-      if (c >= ncand_apply) continue;
-#else
-    for (u32 c = tid; c < ncand_apply; c += BLK) {
-#endif
+    for (u32 c = tid; c < ncand_apply; c += VSR_BLOCK) {
       const u32 code = s_cand2[c];
       const int p = (int)((code >> 11) & 127), ord = (int)(code & 2047);
       const u64* rec = s_rec + p * stride;
@@ -1138,7 +981,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         raise_error(ctl, D.err, ((p_base + (u64)p) << 16) | (u64)ord);
         continue;
       }
-      if constexpr (PLAIN == 6) {                                 // probe-only: a successor that fails an invariant is written down for k_probe_resolve, nothing else happens here
+      if constexpr (PLAIN == EXPAND_PROBE) {                                 // probe-only: a successor that fails an invariant is written down for k_probe_resolve, nothing else happens here
         if (Ops::invariants(M, rec, D) != 0) {
           const u64 i = atomicAdd((unsigned long long*)&ctl->n_pending, 1ull);
           if (i < pending_cap) { pending[2 * i] = origin_make(p_base + (u64)p, ord); pending[2 * i + 1] = 0; }   // (p_offset is 0 for this instantiation, or the tile list)
@@ -1202,9 +1045,9 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           } else {
             remote = true;                                      // (no winner set: the owner grants the regeneration, rounds 3-4)
           }
-        } else if (mode == MODE_REGEN && PLAIN == 0 && wset) {
+        } else if (mode == MODE_REGEN && PLAIN == EXPAND_GENERAL && wset) {
           do_write = wset_take(wset, fp, level, wepoch);        // the same rule for the states this rank owns itself: no seen-set access in a sharded regeneration
-        } else if (PLAIN == 3) {
+        } else if (PLAIN == EXPAND_REGEN_BITS) {
           // The first seen-set-only level, unsharded (round 5): the pass that INSERTED it left one bit per (parent, ordinal) whose lane made a state
           // (`filter` / `fmask` carry the bitmap and its words per parent here — an unsharded pass has no sent-filter).  That instance rebuilds the
           // state: no seen-set access at all, exactly once by construction (a state has one inserting lane).
@@ -1223,14 +1066,14 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           }
           do_write = claimed;
           claimed_now = claimed;
-          if (PLAIN == 0 && wset && claimed && !wset_insert(wset, fp, level)) raise_error(ctl, ERR_TABLE_FULL, fp);   // a state this rank's own lane made
-          if (PLAIN == 4 && filter && claimed)   // unsharded virtual level: remember WHICH instance made the state (see PLAIN == 3 above)
+          if (PLAIN == EXPAND_GENERAL && wset && claimed && !wset_insert(wset, fp, level)) raise_error(ctl, ERR_TABLE_FULL, fp);   // a state this rank's own lane made
+          if (PLAIN == EXPAND_INSERT && filter && claimed)   // unsharded virtual level: remember WHICH instance made the state (see PLAIN == EXPAND_REGEN_BITS above)
             atomicOr(&((u32*)filter)[(p_offset + p_base + (u64)p) * fmask + ((u32)ord >> 5)], 1u << ((u32)ord & 31u));
         }
         // the ONE evaluation of the invariants (three inlined copies pushed the mode-capable kernels out of the instruction cache)
         int bad = (check || do_write || (remote && mode == MODE_INSERT)) ? Ops::invariants(M, rec, D) : 0;
 #ifdef VSRMC_TEST_HOOKS                                       // test hook (Model::test_bad_fp): only in the library built with -DVSRMC_TEST_HOOKS (libvsrmc_hooks.so)
-        if constexpr (PLAIN == 0)
+        if constexpr (PLAIN == EXPAND_GENERAL)
           if (M.test_bad_mask && fp == M.test_bad_fp && (check || do_write || remote)) bad |= (int)M.test_bad_mask;
 #endif
         if (mode == MODE_PROBE) {
@@ -1264,7 +1107,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
         const u64 a_3 = VSR_CLK();
         if (tid == 0) s_acc[12] += a_3 - a_2;
         u64 idx = 0;
-        // Since round 6 the ordinary level's instantiation (PLAIN == 1) copies the parent words of the successors a wave writes in a round with the WHOLE wave —
+        // COOP (round 6): the ordinary level's instantiations copy the parent words of the successors a wave writes in a round with the WHOLE wave —
         // lane k moves word k of one record per instruction: one contiguous 350-byte store instead of twenty-two 16-byte stores of the claiming lane alone, and
         // the LDS reads of different records are independent of each other (the lane-serial copy waits for its own LDS read in every trip).  The claiming lane
         // then writes its patches on top (same wave, program order).  Lanes that left the body earlier (errors) take no part: the words are shared out over the
@@ -1307,17 +1150,6 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           // parent from LDS, 16 bytes per store (records are 8-byte aligned), then the patches on top (same lane: ordered)
             typedef u64 u64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
             int k = 0;
-#if VSR_COPY8
-            for (; k + 7 < plen; k += 8) {                        // EXPERIMENT: eight words per trip, four LDS reads in flight (round 3 lost registers to this; MachineLICM off leaves room)
-              u64x2_a8 a0, a1, a2, a3;
-              a0.x = rec[k]; a0.y = rec[k + 1]; a1.x = rec[k + 2]; a1.y = rec[k + 3];
-              a2.x = rec[k + 4]; a2.y = rec[k + 5]; a3.x = rec[k + 6]; a3.y = rec[k + 7];
-              *(u64x2_a8*)(out + k) = a0;
-              *(u64x2_a8*)(out + k + 2) = a1;
-              *(u64x2_a8*)(out + k + 4) = a2;
-              *(u64x2_a8*)(out + k + 6) = a3;
-            }
-#endif
             if (plen - k >= 2) {
               u64x2_a8 cur;
               cur.x = rec[k];
@@ -1364,7 +1196,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           }
           if ((u32)hdr_nmsg(D.hdr) > s_maxbag_out) atomicMax(&s_maxbag_out, (u32)hdr_nmsg(D.hdr));
         }
-        if (PLAIN == 0 && remote) {
+        if (PLAIN == EXPAND_GENERAL && remote) {
           // announce (fp, key) to the owner: entry i of the block's chunk of that owner's bucket
           u64 i = 0;
           for (;;) {
@@ -1426,9 +1258,9 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       } else {
         s_chunk_used += s_tile_cursor;
       }
-      s_acc[0] += PLAIN == 6 ? s_ntotal : s_ncand;
+      s_acc[0] += PLAIN == EXPAND_PROBE ? s_ntotal : s_ncand;
       s_acc[1] += s_dead;
-      if (PLAIN != 6) s_acc[2] += ncand_apply;                   // one home-slot probe per applied candidate
+      if (PLAIN != EXPAND_PROBE) s_acc[2] += ncand_apply;                   // one home-slot probe per applied candidate
       const u64 t_5 = VSR_CLK();
       s_acc[3] += t_1 - t_0;
       s_acc[4] += t_2 - t_1;
@@ -1437,16 +1269,14 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
       s_acc[7] += t_5 - t_4;
     }
     if (tid < 16) s_acc[16 + tid] += s_kcount[tid];
-#if !VSR_NO_TAIL_SYNC
-    VSR_SYNC_G(0);
-#endif
+    // (no barrier at the bottom of the tile loop: what follows the apply-closing barrier touches LDS words of wave 0 only)
   }
   // ---- block epilogue: invalidate the unused tail of the chunk, flush the accumulators
   {
     if (fused) {
       const u32 used = s_ich_used;
       const u64 base = s_ich_base;
-      for (u32 k = used + tid; k < ichunk; k += BLK) {
+      for (u32 k = used + tid; k < ichunk; k += VSR_BLOCK) {
         nx_off[base + k] = 0;
         lvl_fp[base + k] = 0;
       }
@@ -1457,7 +1287,7 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
           const u64 base = st >> 24;
           const u32 used = (u32)(st & 0xFFFFFFull) < cchunk ? (u32)(st & 0xFFFFFFull) : cchunk;
           if (base == CS_NONE) continue;
-          for (u32 k = used + tid; k < cchunk; k += BLK) {
+          for (u32 k = used + tid; k < cchunk; k += VSR_BLOCK) {
             cand_send[2 * ((u64)o * cand_cap + base + k)] = 0;  // fingerprint 0 = no candidate
             cand_send[2 * ((u64)o * cand_cap + base + k) + 1] = ~(u64)0;
           }
@@ -1477,11 +1307,8 @@ k_expand(Model Marg, const u64* __restrict__ fr_words, const u64* __restrict__ f
     } else {
       const u32 used = s_chunk_used;
       const u64 base = s_chunk_base;
-      for (u32 k = used + tid; k < pchunk; k += BLK) pending[3 * (base + k) + 1] = ~(u64)0;
+      for (u32 k = used + tid; k < pchunk; k += VSR_BLOCK) pending[3 * (base + k) + 1] = ~(u64)0;
     }
-#if VSR_NO_FLUSH     // EXPERIMENT (timing only: the level's reported figures are wrong): how much of a launch is the drain of the per-block statistics?
-    if (tid >= 0) return;
-#endif
     if (tid == 0) {
       if (s_acc[0]) atomicAdd((unsigned long long*)&ctl->generated, s_acc[0]);
       if (s_acc[1]) atomicAdd((unsigned long long*)&ctl->deadlocks, s_acc[1]);

@@ -70,7 +70,6 @@ struct RcclCtx {
   char* d_stage = nullptr;       // (world + 1) * STAGE bytes: small all-gathers
   hipStream_t stream = nullptr;  // for the small all-gathers; all-to-all-v runs on the stream the loop passes
   enum { STAGE = 512 };
-  bool always_call = false;      // issue the collectives even at world 1 (latency measurements)
 };
 const int NCCL_CHAR = 0;         // ncclInt8 / ncclChar
 
@@ -78,7 +77,7 @@ int rccl_alltoallv(void* vctx, const void* send, const uint64_t* scnt, const uin
                    const uint64_t* roff, uint32_t eb, void* stream) {
   RcclCtx* x = (RcclCtx*)vctx;
   RcclApi* a = rccl_api();
-  if (x->world == 1 && !x->always_call) return 0;                // nobody to talk to
+  if (x->world == 1) return 0;                                   // nobody to talk to
   int rc = a->GroupStart();
   for (int p = 0; p < x->world && rc == 0; p++) {
     if (p == x->rank) continue;
@@ -94,7 +93,7 @@ int rccl_allgather(void* vctx, const void* send, void* recv, uint32_t bytes) {
   RcclCtx* x = (RcclCtx*)vctx;
   RcclApi* a = rccl_api();
   if (bytes > RcclCtx::STAGE) return fail(VSRMC_E_ARG, "all-gather record larger than the staging buffer");
-  if (x->world == 1 && !x->always_call) { std::memcpy(recv, send, bytes); return 0; }   // VSRMC_COMM_ALWAYS_CALL=1: measure the collective's latency at world 1
+  if (x->world == 1) { std::memcpy(recv, send, bytes); return 0; }
   if (hipMemcpyAsync(x->d_stage, send, bytes, hipMemcpyHostToDevice, x->stream) != hipSuccess) return fail(VSRMC_E_HIP, "all-gather staging copy");
   const int rc = a->AllGather(x->d_stage, x->d_stage + RcclCtx::STAGE, bytes, NCCL_CHAR, x->comm, x->stream);
   if (rc != 0) return fail(VSRMC_E_HIP, std::string("RCCL all-gather: ") + (a->GetErrorString ? a->GetErrorString(rc) : "?"));
@@ -349,7 +348,6 @@ int32_t vsrmc_comm_rccl_create(const uint8_t* id128, int32_t rank, int32_t world
   HIPCHK(hipSetDevice(device));
   RcclCtx* x = new RcclCtx();
   x->rank = rank; x->world = world; x->device = device;
-  x->always_call = std::getenv("VSRMC_COMM_ALWAYS_CALL") != nullptr;
   RcclId128 id;
   std::memcpy(id.b, id128, 128);
   int rc = a->CommInitRank(&x->comm, world, id, rank);
