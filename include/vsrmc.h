@@ -258,6 +258,35 @@ int32_t vsrmc_checker_lookup(vsrmc_checker* c, uint64_t key, int32_t level, int3
 int32_t vsrmc_checker_find_fp(vsrmc_checker* c, uint64_t fp, uint64_t* index);
 void vsrmc_checker_destroy(vsrmc_checker* c);
 
+/* ---- terminal states ≙ TLC's deadlock check (-deadlock / CHECK_DEADLOCK) with its counter-example ------------------------------
+ * A state is TERMINAL when no (action, binding) instance is enabled in it — what vsrmc_level_info.deadlocks counts and where a simulation
+ * walk ends.  k_terminal (csrc/vsr_terminal.hpp) finds them with a guards-only scan: no action applied, the seen-set untouched.
+ * flags[i]: bit 0 = record i has no enabled (action, binding) instance; bit 1 = AllReplicasMoveToSameView (VSR.tla:958-962) is false in it.
+ * A terminal state with bit 1 set is a counter-example to ViewChangeCompletes (VSR.tla:964-968) — the behaviour that stutters in it is fair;
+ * finding none is no verdict: behaviours that loop are not examined.
+ * vsrmc_terminal_batch: n wire records of the caller.
+ * vsrmc_checker_terminal_scan: the newest STORED level, from the record buffer (HBM or pinned host memory).  Valid wherever
+ *   vsrmc_checker_level_fps is, any number of times; changes nothing a later call can observe.  n_terminal of a scan of level L equals
+ *   `deadlocks` of the step that then expands level L.  VSRMC_E_STATE on a sharded checker and while the deepest complete level exists in the
+ *   seen-set only (after vsrmc_checker_deepen): those levels have no records, their terminal states stay counted.  The counter-example is
+ *   vsrmc_checker_trace_fp(c, level, min_fp, ...) — the smallest fingerprint of the shallowest level that has a terminal state: the same state
+ *   in every run, under every buffer size, in either level scheme.
+ * vsrmc_checker_terminal_states: the terminal states the last scan found, fingerprints ascending (the rule of vsrmc_checker_probe_violators);
+ *   fps == NULL asks for the number.  The scan keeps at most 2^20 of them: when the level has more, *n is still the true number, the call
+ *   copies the ones held, returns VSRMC_E_REP and says so in vsrmc_last_error(); the scan's counters and minima are exact regardless.
+ *   (Test knob: the environment variable VSRMC_TERMINAL_LIST_CAP=N, read by every scan, lowers the 2^20 to N so that the overflow path can be
+ *   reached on a small space; it has no other use.) */
+int32_t vsrmc_terminal_batch(const vsrmc_model* m, int32_t device, const uint64_t* words, const uint64_t* off, uint64_t n, uint8_t* flags);
+typedef struct vsrmc_terminal_info {
+  int32_t level, reserved0;                        /* the level scanned = the newest STORED level */
+  uint64_t n_states, n_terminal, n_unsettled;      /* n_unsettled counts terminal states only */
+  uint64_t min_fp, min_index;                      /* smallest fingerprint among the terminal states, its index in the level; ~0 if none */
+  uint64_t min_fp_unsettled, min_index_unsettled;
+  double kernel_ms;                                /* HIP-event time of k_terminal */
+} vsrmc_terminal_info;
+int32_t vsrmc_checker_terminal_scan(vsrmc_checker* c, vsrmc_terminal_info* out);
+int32_t vsrmc_checker_terminal_states(vsrmc_checker* c, uint64_t* fps, uint8_t* flags, uint64_t cap, uint64_t* n);
+
 /* Probe level: expand the newest level without storing its successors — invariants are evaluated on every successor that is
  * not a state of an earlier level, nothing is inserted or written, so the level costs no frontier memory; the search cannot
  * continue afterwards.  Finds a violation one level beyond what memory can hold.  Also valid right after a step that failed

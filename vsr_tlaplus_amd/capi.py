@@ -37,6 +37,15 @@ class LevelInfo(C.Structure):
         return d
 
 
+class TerminalInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("n_terminal", C.c_uint64),
+                ("n_unsettled", C.c_uint64), ("min_fp", C.c_uint64), ("min_index", C.c_uint64), ("min_fp_unsettled", C.c_uint64),
+                ("min_index_unsettled", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved0"}
+
+
 class ShardIO(C.Structure):
     _fields_ = [("cand_send", C.c_void_p), ("cand_cap", C.c_uint64)]
 
@@ -107,6 +116,9 @@ SYMBOLS = {
     "vsrmc_checker_level_checksum": (C.c_int32, [V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vsrmc_checker_select": (C.c_int32, [V, C.c_uint32, C.c_uint64, V, C.c_uint64, V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vsrmc_checker_find_fp": (C.c_int32, [V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_terminal_batch": (C.c_int32, [V, C.c_int32, V, V, C.c_uint64, V]),
+    "vsrmc_checker_terminal_scan": (C.c_int32, [V, C.POINTER(TerminalInfo)]),
+    "vsrmc_checker_terminal_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_check": (C.c_int32, [V, C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(LevelInfo)]),
     "vsrmc_queue_create": (C.c_int32, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(V)]),
     "vsrmc_queue_enqueue_batch": (C.c_int32, [V, V, V, C.c_uint64]),

@@ -123,6 +123,16 @@ class Model:
         check(capi.load().vsrmc_fingerprint_batch(self._h, device, _p(words), _p(off), n, _p(fps), _p(aks)))
         return fps, aks
 
+    def terminal_flags(self, words, off, device=0):
+        """One flag byte per state of a batch (k_terminal, guards only): bit 0 = terminal — no (action, binding) instance is enabled (TLC's
+        deadlock); bit 1 = unsettled — AllReplicasMoveToSameView (VSR.tla:958-962) is false."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        flags = np.zeros(max(1, n), dtype=np.uint8)
+        check(capi.load().vsrmc_terminal_batch(self._h, device, _p(words), _p(off), n, _p(flags)))
+        return flags[:n]
+
     def tlc_fingerprints(self, words, off, device=0):
         """TLC's own fingerprint (tlc2.util.FP64 over Value.fingerPrint of `view`; [TLC-RECALLED], csrc/vsr_tlcfp.hpp) of a batch of states,
         computed on the GPU.  With SYMMETRY: of the permuted state TLC picks (tlc_min_permutation)."""
@@ -341,6 +351,7 @@ class ModelChecker:
             self.levels = [dict(level=info.level, n_new=info.n_new, generated=0, deadlocks=0, recovered=True)]
             self.violation = None
             self.rebased = []
+            self.deadlock = None
             self.depth = self.level + info.reserved0               # a deep search: the levels beyond the stored one came along in the seen-set
         check(capi.load().vsrmc_checker_options(self._h, C.byref(o)))       # sizes left 0 were derived from the free device memory
 
@@ -356,6 +367,7 @@ class ModelChecker:
         self.levels = [dict(level=1, n_new=1, generated=0, deadlocks=0)]
         self.violation = None
         self.rebased = []
+        self.deadlock = None
 
     def reset(self):
         """Back to Init with an empty seen-set; keeps the HBM allocations (a fresh TLC run on the same model)."""
@@ -441,9 +453,11 @@ class ModelChecker:
             check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))
         return st.value
 
-    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True):
+    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False):
         """Worker.run until the queue is empty, an invariant is violated, or a bound is hit — the automatic level scheme: levels are
-        stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen)."""
+        stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen).
+        check_deadlock (TLC's default, off here): every stored level is scanned for terminal states before it is expanded; the first level
+        that has one ends the run with "deadlock" — self.deadlock = the scan's result, deadlock_trace() the behaviour."""
         import time
         t0 = time.time()
         while True:
@@ -453,6 +467,10 @@ class ModelChecker:
                 return "max-seconds"
             if self.room() == 2:
                 return "seen-set-full"
+            if check_deadlock and self.depth == self.level and self.n_frontier:
+                t = self.terminal_scan()
+                if t["n_terminal"]:
+                    return "deadlock"
             kind, d, p = self.advance()
             if d["n_new"] == 0:
                 return "exhausted"
@@ -463,6 +481,41 @@ class ModelChecker:
         """the counter-example of the violation run() / advance() reported, wherever it was found"""
         v = self.violation
         return self.probe_trace() if v.get("probed") else self.trace(v["level"], v["index"])
+
+    def terminal_scan(self):
+        """Scan the newest stored level for terminal states (k_terminal: guards only, nothing applied, the seen-set untouched) -> dict(level,
+        n_states, n_terminal, n_unsettled, min_fp, min_index, min_fp_unsettled, min_index_unsettled, kernel_ms); fingerprints / indices are
+        None where there is no such state.  n_terminal == `deadlocks` of the step that expands this level.  Remembers the first level that
+        has a terminal state as self.deadlock (the shallowest level, there the smallest fingerprint: the same state in every run)."""
+        info = capi.TerminalInfo()
+        check(capi.load().vsrmc_checker_terminal_scan(self._h, C.byref(info)))
+        d = info.as_dict()
+        for k in ("min_fp", "min_index", "min_fp_unsettled", "min_index_unsettled"):
+            if d[k] == (1 << 64) - 1:
+                d[k] = None
+        if d["n_terminal"] and (self.deadlock is None or d["level"] < self.deadlock["level"]):
+            self.deadlock = d
+        return d
+
+    def terminal_states(self):
+        """The terminal states the last terminal_scan() found -> (fingerprints ascending, flag bytes: bit 0 set, bit 1 = unsettled)."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_terminal_states(self._h, None, None, 0, C.byref(n))
+        if rc not in (0, -5):                                             # -5 (VSRMC_E_REP): more than the list holds — raised below, by the call that copies
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        flags = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_terminal_states(self._h, _p(fps), _p(flags), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), flags[: n.value].copy()
+
+    def deadlock_trace(self):
+        """The behaviour into the terminal state terminal_scan() / run(check_deadlock=True) reported (self.deadlock): [(action name, record)]
+        from Init, the shape of violation_trace()."""
+        d = self.deadlock
+        if d is None:
+            raise ValueError("no terminal state has been found (terminal_scan)")
+        return self.trace_fp(d["level"], d["min_fp"])
 
     def level_fps(self):
         out = np.zeros(max(1, self.n_frontier), dtype=np.uint64)

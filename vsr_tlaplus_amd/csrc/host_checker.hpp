@@ -98,6 +98,12 @@ struct vsrmc_checker {
                                          // seen-set and vsrmc_checker_advance keeps it as a seen-set-only level (host_search.hpp: adopt_overflowed_level)
   u64 hist_new[2] = {0, 0};              // new states of the last two levels (growth estimate of vsrmc_checker_advance)
   u64 g_last = 16, cur_rec_w = 0;        // successors generated per expanded state of the last level (rounded up, + 1); words of the newest level's records
+  // the last vsrmc_checker_terminal_scan (host_terminal.hpp): the terminal states it listed (fingerprints ascending, a flag byte beside each), how many
+  // the level has in all, and the level scanned (-1: no scan yet)
+  std::vector<u64> term_fps;
+  std::vector<uint8_t> term_flags;
+  u64 term_total = 0;
+  int term_level = -1;
   u64 words_cap(int b) const { return (b == 1 && opt.frontier_words_b) ? opt.frontier_words_b : opt.frontier_words; }
 };
 

@@ -21,6 +21,7 @@
 #include "vsr_parse.hpp"
 #include "vras_parse.hpp"
 #include "vsr_kernels.hpp"
+#include "vsr_terminal.hpp"
 
 #define VSRMC_FP_VERSION 2          // fingerprint function of this build; checkpoints of another version are refused
 
@@ -110,4 +111,5 @@ extern "C" {
 #include "host_checkpoint.hpp"   // checkpoint / recover, accessors, traces, destroy
 #include "vsr_shard_loop.hpp"    // the sharded level loop in C++ over RCCL / host callbacks
 #include "host_tlcfp.hpp"        // TLC's FP64 as a mode
+#include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

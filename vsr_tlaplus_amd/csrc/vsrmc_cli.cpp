@@ -3,7 +3,9 @@
 // ≙ `java -cp tla2tools.jar tlc2.TLC -config VSR.cfg VSR.tla -deadlock` (README:20 of the reference).  Output follows TLC's
 // wording (progress lines, "Invariant ... is violated", "State k: <Action>" + the state in TLC value syntax, final counts).
 // `-deadlock` (= do NOT check deadlock) is the default here because the spec has terminal states; pass
-// -checkDeadlock to stop at the first state without successors like stock TLC would.
+// -checkDeadlock to stop at the first state without successors like stock TLC would: the newest level is scanned for terminal states before it is
+// expanded (vsrmc_checker_terminal_scan) and the behaviour into the one with the smallest fingerprint is printed.  -terminalReport scans every
+// stored level without stopping.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +27,11 @@ static void usage() {
       "usage: vsrmc -config <file.cfg> <spec.tla> [options]\n"
       "  -config FILE      TLC configuration (grammar of VSR.cfg: CONSTANTS / INIT / NEXT / VIEW / SYMMETRY / INVARIANT)\n"
       "  -deadlock         do not check for deadlock (default)      -checkDeadlock   report the first terminal state\n"
+      "                    (= CHECK_DEADLOCK TRUE in the cfg): every stored level is scanned before it is expanded; exit 11 with the behaviour\n"
+      "                    that leads into the terminal state of the smallest fingerprint (-dumpTrace tla FILE writes it)\n"
+      "  -terminalReport   scan every stored level for terminal states without stopping; one summary line at the end.  A terminal state in\n"
+      "                    which AllReplicasMoveToSameView is false is printed with its behaviour (last line: Stuttering): a counter-example\n"
+      "                    to ViewChangeCompletes.  Finding none is no verdict: behaviours that loop are not examined\n"
       "  -maxDepth N       stop after N BFS levels (Init = level 1)\n"
       "  -device D         HIP device ordinal (default 0)\n"
       "  -gpus N           N > 1: run the sharded checker on N GPUs of this node (re-executes as\n"
@@ -116,7 +123,7 @@ int main(int argc, char** argv) {
   std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
-  bool check_deadlock = false, no_tla = false, json = false, simulate = false, host_frontier = false, probe_last = false, coverage = false, audit = false;
+  bool check_deadlock = false, no_tla = false, json = false, simulate = false, host_frontier = false, probe_last = false, coverage = false, audit = false, terminal_report = false;
   int sim_depth = 100;
   unsigned sim_walkers = 1u << 17;
   unsigned long long sim_seed = 1;
@@ -156,6 +163,7 @@ int main(int argc, char** argv) {
     else if (a == "-json") json = true;
     else if (a == "-coverage") coverage = true;
     else if (a == "-audit") audit = true;
+    else if (a == "-terminalReport") terminal_report = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -326,6 +334,56 @@ int main(int argc, char** argv) {
     else std::printf("Checkpointing of run %s completed (level %d).\n", chk_file.c_str(), level);
     t_chk = std::chrono::steady_clock::now();
   };
+  // terminal states (-checkDeadlock / -terminalReport): the newest stored level is scanned before it is expanded
+  struct TermRow { int level; unsigned long long n_terminal, n_unsettled; };
+  std::vector<TermRow> term_rows;
+  vsrmc_terminal_info ti;
+  std::memset(&ti, 0, sizeof(ti));
+  int last_scanned = 0, uns_level = 0, levels_scanned = 0;
+  uint64_t uns_fp = 0;
+  unsigned long long unlisted_levels = 0, unlisted_deadlocks = 0;
+  bool scanned_this_step = false;
+  auto scan_newest = [&]() -> int {                               // 0, or the error of the scan; a level without records is counted, not listed
+    scanned_this_step = false;
+    vsrmc_level_info st;
+    if (vsrmc_checker_status(c, &st) != 0) return -1;
+    if (st.reserved0 != 0 || st.level == last_scanned || st.n_new == 0) return 0;
+    const int32_t r = vsrmc_checker_terminal_scan(c, &ti);
+    if (r == VSRMC_E_STATE) return 0;
+    if (r != 0) return r;
+    last_scanned = ti.level;
+    levels_scanned++;
+    scanned_this_step = true;
+    if (ti.n_terminal) term_rows.push_back(TermRow{ti.level, (unsigned long long)ti.n_terminal, (unsigned long long)ti.n_unsettled});
+    if (ti.n_unsettled && !uns_level) { uns_level = ti.level; uns_fp = ti.min_fp_unsettled; }
+    return 0;
+  };
+  // Init .. the level-`level` state `fp`, printed the way a violation is; `stutter`: a last line "State k+1: Stuttering"
+  auto print_behaviour_to = [&](int level, uint64_t fp, bool stutter) -> bool {
+    uint64_t cap_w = ((uint64_t)level + 2) * (uint64_t)lay.max_record_words, n_states = 0;
+    std::vector<uint64_t> words(cap_w), off((size_t)level + 2);
+    std::vector<int32_t> acts((size_t)level + 2);
+    if (vsrmc_checker_trace_fp(c, level, fp, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states) != 0) {
+      std::printf("Error: %s\n", vsrmc_last_error());
+      return false;
+    }
+    std::printf("Error: The behavior up to this point is:\n");
+    for (uint64_t t = 0; t < n_states; t++) {
+      int64_t need = 0;
+      vsrmc_model_format_state(m, &words[off[t]], nullptr, 0, &need);
+      std::string buf((size_t)need, '\0');
+      vsrmc_model_format_state(m, &words[off[t]], &buf[0], need, &need);
+      std::printf("State %llu: <%s>\n%s\n\n", (unsigned long long)(t + 1), vsrmc_action_name(acts[t]), buf.c_str());
+    }
+    if (stutter) std::printf("State %llu: Stuttering\n", (unsigned long long)(n_states + 1));
+    if (!dump_trace_file.empty()) {
+      if (write_trace_expression(dump_trace_file, m, words, off, acts, n_states))
+        std::printf("The counter-example was written to %s (TLA+ trace expression).\n", dump_trace_file.c_str());
+      else
+        std::printf("Warning: cannot write %s\n", dump_trace_file.c_str());
+    }
+    return true;
+  };
   while (depth < max_depth) {
     if ((probe2_at > 0 && depth + 1 == probe2_at) || (probe3_at > 0 && depth + 1 == probe3_at)) {
       const int nv = probe3_at > 0 && depth + 1 == probe3_at ? 2 : 1;        // virtual levels before the probed one
@@ -365,6 +423,11 @@ int main(int argc, char** argv) {
     if (rc != 0) break;
     if (room == 1 && !json) std::printf("The seen-set was re-hashed into twice the slots.\n");
     if (room == 2) { incomplete = true; break; }
+    if (check_deadlock || terminal_report) {
+      rc = scan_newest();
+      if (rc != 0) break;
+      if (check_deadlock && scanned_this_step && ti.n_terminal) { deadlocked = true; break; }
+    }
     rc = vsrmc_checker_advance(c, &info, &probed, &what);
     if (rc != 0) break;
     if (what == 3) {                                              // no new level: the deep search was re-based (the levels shrink again)
@@ -379,6 +442,7 @@ int main(int argc, char** argv) {
       if (info.n_new == 0) break;
       depth = info.level;
       rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
+      if (terminal_report && !scanned_this_step) { unlisted_levels++; unlisted_deadlocks += (unsigned long long)info.deadlocks; }   // the level this pass expanded has no records
       if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -410,7 +474,11 @@ int main(int argc, char** argv) {
     if (info.n_new) depth = info.level;
     if (info.n_new) rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (json)
+    if (json && scanned_this_step)                                // (terminal / unsettled: of the level this step expanded, like deadlocks)
+      std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu, \"seconds\": %.4f}\n",
+                  info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
+                  (unsigned long long)info.deadlocks, (unsigned long long)ti.n_terminal, (unsigned long long)ti.n_unsettled, dt);
+    else if (json)
       std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
                   (unsigned long long)info.deadlocks, dt);
@@ -423,6 +491,9 @@ int main(int argc, char** argv) {
     if (info.n_new == 0) break;
     checkpoint_now(info.level);
   }
+  // the report covers the newest stored level too when the loop ended before expanding it (-maxDepth, a violation, a full seen-set); an exhausted search's
+  // last level is empty and a level already scanned is not scanned again (scan_newest)
+  if (terminal_report && rc == 0 && !deadlocked) rc = scan_newest();
   double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   int exit_code = 0;
   if (rc != 0) {
@@ -457,6 +528,9 @@ int main(int argc, char** argv) {
       }
       exit_code = 12;   // TLC's exit code for a safety violation
     }
+  } else if (deadlocked && scanned_this_step && ti.n_terminal) {  // found by the scan, before the level was expanded: there is a behaviour to show
+    std::printf("Error: Deadlock reached (%llu state(s) of level %d have no successor).\n", (unsigned long long)ti.n_terminal, ti.level);
+    exit_code = print_behaviour_to(ti.level, ti.min_fp, false) ? 11 : 1;
   } else if (deadlocked) {
     std::printf("Error: Deadlock reached (%llu state(s) of level %d have no successor).\n", (unsigned long long)info.deadlocks, info.level - 1);
     exit_code = 11;
@@ -466,6 +540,30 @@ int main(int argc, char** argv) {
     exit_code = 4;
   } else if (info.n_new == 0) {
     std::printf("Model checking completed. No error has been found.\n");
+  }
+  if (terminal_report && rc == 0) {
+    unsigned long long n_term = 0, n_uns = 0;
+    for (const TermRow& r : term_rows) { n_term += r.n_terminal; n_uns += r.n_unsettled; }
+    std::printf("Terminal report: %llu terminal states in %zu of %d scanned levels", n_term, term_rows.size(), levels_scanned);
+    if (!term_rows.empty()) {
+      std::printf(" (");
+      for (size_t k = 0; k < term_rows.size(); k++) std::printf("%slevel %d: %llu", k ? ", " : "", term_rows[k].level, term_rows[k].n_terminal);
+      std::printf(")");
+    }
+    std::printf(", %llu unsettled (AllReplicasMoveToSameView false).\n", n_uns);
+    if (unlisted_levels)
+      std::printf("%llu level(s) were expanded from the seen-set alone (the parents of the Virtual lines): %llu terminal states counted, not listed.  "
+                  "Probed levels are not expanded: their terminal states are neither counted nor listed.\n", unlisted_levels, unlisted_deadlocks);
+    if (probe2_at > 0 || probe3_at > 0)
+      std::printf("The levels of -probe2At / -probe3At were not scanned: they have no records.\n");
+    if (uns_level) {
+      std::printf("A terminal state of level %d has AllReplicasMoveToSameView false: the behaviour below reaches it and stutters there for ever, which is fair under "
+                  "WF_vars(Next) — a counter-example to ViewChangeCompletes.\n", uns_level);
+      if (!print_behaviour_to(uns_level, uns_fp, true)) exit_code = exit_code ? exit_code : 1;
+    } else {
+      std::printf("No terminal state with AllReplicasMoveToSameView false was found: this is no verdict on ViewChangeCompletes (a behaviour that never reaches a "
+                  "terminal state could still violate it; loops are not examined).\n");
+    }
   }
   if (coverage) {   // ≙ tlc2.TLC -coverage, per action of Next: successors generated in the stored levels (probed / virtual levels not included)
     std::printf("The coverage statistics (successors generated per action):\n");
