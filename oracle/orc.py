@@ -200,12 +200,17 @@ def normalise(P, rec):
     return out[:n].copy()
 
 
+_succ_buf = []
+
+
 def successors(P, rec):
-    """-> list of dict(action, fp, auxkey, inv, words=np.uint64 array) in Next order."""
+    """-> list of dict(action, fp, auxkey, inv, words=np.uint64 array) in Next order.  Not reentrant: the C side writes into one pair of
+    module-level buffers (allocating 0.5 MB per call cost more than the call), every record is copied out before it returns."""
     rec = np.ascontiguousarray(rec, dtype=np.uint64)
     cap_w, cap_s = 1 << 16, 512
-    words = np.zeros(cap_w, dtype=np.uint64)
-    meta = np.zeros(5 * cap_s, dtype=np.uint64)
+    if not _succ_buf:                                   # (one pair of output buffers per process: every successor is copied out of them below)
+        _succ_buf.extend((np.zeros(cap_w, dtype=np.uint64), np.zeros(5 * cap_s, dtype=np.uint64)))
+    words, meta = _succ_buf
     used = C.c_int()
     n = lib().orc_successors(C.c_void_p(P.ptr), C.c_void_p(rec.ctypes.data), C.c_void_p(words.ctypes.data), cap_w,
                              C.c_void_p(meta.ctypes.data), cap_s, C.byref(used))

@@ -262,3 +262,9 @@ def test_test_hooks_live_in_the_hooks_library_only(vt):
     lib = C.CDLL(os.path.join(here, "libvsrmc_hooks.so"))
     for name in capi.SYMBOLS:
         assert hasattr(lib, name), name
+    # the entry point that seeds a search with a caller's records (csrc/host_test_seed.hpp, tests/test_deep_actions_gpu.py): hooks library only
+    plib = C.CDLL(os.path.join(here, "libvsrmc.so"))
+    for name in capi.HOOK_SYMBOLS:
+        assert hasattr(lib, name), name
+        assert not hasattr(plib, name) and name.encode() not in prod, name
+    assert b"vsrmc_test_" not in prod

@@ -175,6 +175,11 @@ SYMBOLS = {
     "vsrmc_shard_loop_probe_trace_fps": (C.c_int32, [V, V, C.c_int32, C.POINTER(C.c_int32)]),
 }
 
+# test hooks: exported by libvsrmc_hooks.so only (-DVSRMC_TEST_HOOKS; VSRMC_LIB points a test's child process at it), declared when present
+HOOK_SYMBOLS = {
+    "vsrmc_test_checker_seed_records": (C.c_int32, [V, V, V, C.c_uint64]),
+}
+
 _lib = None
 
 
@@ -197,6 +202,11 @@ def load():
             fn = getattr(L, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args) in HOOK_SYMBOLS.items():
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.restype = res
+                fn.argtypes = args
         _lib = L
     return _lib
 

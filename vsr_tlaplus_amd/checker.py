@@ -374,6 +374,20 @@ class ModelChecker:
         check(capi.load().vsrmc_checker_reset(self._h))
         self._fresh()
 
+    def seed_records(self, words, off):
+        """TEST HOOK (the hooks library only: csrc/host_test_seed.hpp): start the search from the wire records words[off[i] : off[i + 1]] instead of
+        Init — they become level 1, the seen-set holds exactly them; step() / probe() / deepen() / terminal_scan() / select() then run as on any level.
+        reset() goes back to Init."""
+        fn = getattr(capi.load(), "vsrmc_test_checker_seed_records", None)
+        if fn is None:
+            raise RuntimeError("vsrmc_test_checker_seed_records is a test hook: load libvsrmc_hooks.so (VSRMC_LIB)")
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        check(fn(self._h, _p(words), _p(off), len(off) - 1))
+        self._fresh()
+        self.n_frontier = self.distinct = len(off) - 1
+        self.levels = [dict(level=1, n_new=len(off) - 1, generated=0, deadlocks=0, seeded=True)]
+
     def step(self):
         info = capi.LevelInfo()
         check(capi.load().vsrmc_checker_step(self._h, C.byref(info)))

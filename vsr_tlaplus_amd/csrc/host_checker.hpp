@@ -104,6 +104,11 @@ struct vsrmc_checker {
   std::vector<uint8_t> term_flags;
   u64 term_total = 0;
   int term_level = -1;
+#ifdef VSRMC_TEST_HOOKS
+  // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
+  std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending
+  std::vector<u64> test_seed_words, test_seed_off;
+#endif
   u64 words_cap(int b) const { return (b == 1 && opt.frontier_words_b) ? opt.frontier_words_b : opt.frontier_words; }
 };
 
@@ -300,6 +305,9 @@ int checker_seed(vsrmc_checker* c) {
   const Model& M = c->model.M;
   // the scratch plan of a deep search points into whichever record buffer was idle when it was made: a search that starts over starts without one
   deep_free_scratch(c);
+#ifdef VSRMC_TEST_HOOKS
+  c->test_seed_index.clear(); c->test_seed_words.clear(); c->test_seed_off.clear();
+#endif
   c->rebase_off = false;
   c->saw_violation = false;
   c->deep = 0;

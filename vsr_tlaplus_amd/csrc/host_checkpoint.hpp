@@ -418,6 +418,9 @@ int32_t vsrmc_checker_select(vsrmc_checker* c, uint32_t action_mask, uint64_t ma
 
 // ≙ the forward half of TLCTrace.getTrace: re-execute `nsteps` ordinals from Init on the GPU (k_replay)
 // re-execute a path from Init: by ordinals (fps == nullptr) or by the fingerprints of its states (fps[0 .. nsteps], fps[0] = Init)
+#ifdef VSRMC_TEST_HOOKS
+static thread_local const u64* g_test_replay_start = nullptr;    // TEST HOOK (host_test_seed.hpp): the wire record the path of a seeded search starts at
+#endif
 static int32_t replay_path(const vsrmc_model* m, int32_t device, const uint32_t* ords, const uint64_t* fps, int32_t nsteps, uint64_t* words,
                            uint64_t cap_words, uint64_t* off, int32_t* actions, uint64_t cap_states, uint64_t* n_states) {
   if (!m || !words || !off || !actions || !n_states || nsteps < 0 || (nsteps && !ords && !fps)) return fail(VSRMC_E_ARG, "bad argument");
@@ -440,6 +443,9 @@ static int32_t replay_path(const vsrmc_model* m, int32_t device, const uint32_t*
   }
   std::vector<u64> wire, dev(512);
   init_record_wire(M, wire);
+#ifdef VSRMC_TEST_HOOKS
+  if (g_test_replay_start) wire.assign(g_test_replay_start, g_test_replay_start + M.h0 + hdr_nmsg(g_test_replay_start[0]));
+#endif
   int len = wire_to_device(M, wire.data(), dev.data());
   u64 H[6];
   hash_full_host(M, (const u64*)dev.data(), H);
@@ -498,6 +504,14 @@ int32_t vsrmc_checker_trace_fp(vsrmc_checker* c, int32_t level, uint64_t fp, uin
   std::vector<u64> fps;
   int rc = walk_trace(c, fp, level, &fps);                     // through the seen-set, back to Init, on the device
   if (rc) return rc;
+#ifdef VSRMC_TEST_HOOKS
+  struct ReplayStart { ~ReplayStart() { g_test_replay_start = nullptr; } } replay_start;
+  if (!c->test_seed_index.empty()) {                           // a seeded search: the path starts at the seed with the fingerprint the walk ended at
+    const auto it = std::lower_bound(c->test_seed_index.begin(), c->test_seed_index.end(), std::make_pair(fps[0], (u64)0));
+    if (it == c->test_seed_index.end() || it->first != fps[0]) return fail(VSRMC_E_STATE, "seeded search: the walk through the seen-set did not end at a seed");
+    g_test_replay_start = c->test_seed_words.data() + c->test_seed_off[it->second];
+  }
+#endif
   return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
 }
 
