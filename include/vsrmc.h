@@ -198,7 +198,8 @@ typedef struct vsrmc_level_info {
   uint64_t limit_rechecked;      /* a probed level: instances outside the invariants' footprint (not applied by a probe pass) that sat in a tile with a record
                                   * at a representation limit — bag within R - 1 entries of its capacity, a delivery count of 3.  Not 0: those passes were
                                   * run AGAIN with every action applied, so a limit hit by such a successor is reported like anywhere else (round 5: it went
-                                  * unreported); 0 on every BASELINE configuration */
+                                  * unreported); 0 on every BASELINE configuration.  (k_probe_scan counts the RECORDS at such a limit that have such an
+                                  * instance, not the instances of their tile: any value but 0 means the same) */
 } vsrmc_level_info;
 
 void vsrmc_options_default(vsrmc_options* o);

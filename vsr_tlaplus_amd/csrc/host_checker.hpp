@@ -59,6 +59,12 @@ struct vsrmc_checker {
   void* modes_kernel = nullptr;          // the same without sharding (expand_pass: the passes of vsrmc_checker_probe / _probe2 / _probe3), or null
   void* regen_bits_kernel = nullptr, *insert_kernel = nullptr;   // ... with ONE mode compiled in (k_expand: PLAIN == 3 / 4), or null
   void* probe_kernel = nullptr;          // ... the probe pass alone, five blocks per CU, failing successors resolved afterwards (PLAIN == 6; k_probe_resolve), or null
+  // the probe pass as kernels of its own (vsr_probe_scan.hpp; R <= 3): k_probe_scan counts and lists the footprint's instances, k_probe_apply runs them, k_probe_resolve
+  // looks the failing successors up.  Null where the configuration has none (or VSRMC_NO_PROBE_KERNEL is set).
+  void* probe_scan_kernel = nullptr, *probe_apply_kernel = nullptr;
+  u64* probe_list = nullptr;             // PSCAN_LIST_HDR words (word 0: entries appended) + probe_list_cap entries, allocated with the checker
+  u64 probe_list_cap = 0;
+  bool probe_scan_off = false;           // the pass in flight overflowed the list: it is being run again by the mode-capable k_expand
   u64 cur_max_bag = 0;                   // largest bag among the records of the newest level (LDS slot size of the next launch)
   bool bag_known = true;                 // false after a checkpoint was loaded or records arrived from other ranks: use the capacity
   // vsrmc_checker_probe / _probe2: where the reported violator's counter-example is walked from — the fingerprint of the deepest
@@ -117,6 +123,8 @@ typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,
                                   const uint8_t*, u64*, u64*, int, u32, u32, int, const u64*);
+typedef void (*ProbeScanKernel)(Model, const u64*, const u64*, u64, LevelCtl*, int, u32, u64*, u64);
+typedef void (*ProbeApplyKernel)(Model, const u64*, const u64*, const u64*, u64, u64*, u64, LevelCtl*);
 // Every instantiation of k_expand and k_materialize, by configuration.  The configurations of BASELINE.json (and their small neighbours used by
 // the tests) have instantiations with the model constants folded in; anything else runs the model's generic ones (SPEC % 1000 == 0).
 struct KernelSet {
@@ -126,11 +134,17 @@ struct KernelSet {
   bool generic;                         // `fused` is generic in the constants (fused_shape: the only one that may run 128-record tiles at R <= 3)
   // unsharded passes (k_expand: EXPAND_*), or null where the configuration has none
   ExpandKernel plain = nullptr, plain5 = nullptr, modes = nullptr, regen_bits = nullptr, insert = nullptr, probe = nullptr;
+  ProbeScanKernel scan = nullptr;       // the probe pass of vsr_probe_scan.hpp (then `probe` is null: the instantiation it replaced is not compiled) ...
+  ProbeApplyKernel apply = nullptr;     // ... and the kernel that applies what it listed
 };
 template <int SPEC>
 KernelSet full_set(ExpandKernel plain5 = nullptr) {             // a model-0 configuration with the whole family of unsharded instantiations
-  return {k_expand<false, SPEC>, k_materialize<SPEC>, k_expand<true, SPEC>, false, k_expand<true, SPEC, EXPAND_PLAIN>, plain5,
-          k_expand<true, SPEC, EXPAND_MODES>, k_expand<true, SPEC, EXPAND_REGEN_BITS>, k_expand<true, SPEC, EXPAND_INSERT>, k_expand<true, SPEC, EXPAND_PROBE>};
+  KernelSet k{k_expand<false, SPEC>, k_materialize<SPEC>, k_expand<true, SPEC>, false, k_expand<true, SPEC, EXPAND_PLAIN>, plain5,
+              k_expand<true, SPEC, EXPAND_MODES>, k_expand<true, SPEC, EXPAND_REGEN_BITS>, k_expand<true, SPEC, EXPAND_INSERT>};
+  // the probe pass: the kernels of vsr_probe_scan.hpp where a record fits 64 words (R <= 3), k_expand's probe-only instantiation elsewhere
+  if constexpr ((SPEC % 1000) / 100 <= 3) { k.scan = k_probe_scan<SPEC>; k.apply = k_probe_apply<SPEC>; }
+  else k.probe = k_expand<true, SPEC, EXPAND_PROBE>;
+  return k;
 }
 KernelSet kernels_for(const Model& M) {
   switch (M.model_id * 1000 + M.R * 100 + M.C * 10 + M.n) {     // (the models 1 and 2 have no clients: C = 0)
@@ -491,6 +505,21 @@ int32_t vsrmc_checker_create(const vsrmc_model* m, const vsrmc_options* o_in, vs
   c->regen_bits_kernel = (void*)ks.regen_bits;
   c->insert_kernel = (void*)ks.insert;
   c->probe_kernel = std::getenv("VSRMC_NO_PROBE_KERNEL") ? nullptr : (void*)ks.probe;   // (tests: the probe passes of the general instantiation)
+  if (ks.scan && ks.apply && !std::getenv("VSRMC_NO_PROBE_KERNEL")) {
+    // the list of footprint instances of one probe pass (2 % of the enabled instances on the README configuration, a tenth of an entry per parent): sized
+    // here — a deep search hands all free memory to its scratch buffers later.  A pass that needs more is run again by k_expand (expand_pass), never cut short.
+    // VSRMC_PROBE_LIST=<entries> (tests): a list so short that this happens.
+    u64 cap = std::max<u64>((u64)1 << 12, std::min<u64>((u64)1 << 24, o->frontier_states / 4));
+    if (const char* ev = std::getenv("VSRMC_PROBE_LIST")) cap = (u64)std::max<long long>(1, std::atoll(ev));
+    if (hipMalloc((void**)&c->probe_list, ((u64)PSCAN_LIST_HDR + cap) * 8) == hipSuccess) {
+      c->probe_list_cap = cap;
+      c->probe_scan_kernel = (void*)ks.scan;
+      c->probe_apply_kernel = (void*)ks.apply;
+    } else {
+      (void)hipGetLastError();
+      c->probe_list = nullptr;
+    }
+  }
   rc = checker_seed(c);
   if (rc) { vsrmc_checker_destroy(c); return rc; }
   *out = c;
@@ -872,6 +901,50 @@ static int32_t step_local(vsrmc_checker* c, vsrmc_level_info* info) {
 }
 
 namespace {
+// how a pass ends: the errors the device raised, the buffers it ran out of
+int pass_verdict(vsrmc_checker* c, int level) {
+  if (!c->h.err && c->h.full) {                                // a pass into buffers that ran out (LevelCtl::full): an error here — the caller sized the slice
+    c->h.err = ERR_FRONTIER_FULL;
+    c->h.err_info = c->h.full_info << 16;
+  }
+  if (c->h.err) return level_error(c, c->h, level);
+  if (c->h.ties) {
+    c->failed = 1;
+    return fail(VSRMC_E_STATE, "two successors of one level share a VIEW fingerprint but differ in the aux variables (SURVEY F2)");
+  }
+  return 0;
+}
+// the end of a probe pass that wrote its failing successors down as (parent, ordinal) entries in `pending` (k_expand<.., EXPAND_PROBE>, k_probe_apply): they are
+// fingerprinted and looked up now (k_probe_resolve); its kernel time is added to the pass's
+int probe_pass_finish(vsrmc_checker* c, const u64* src_words, const u64* src_off, int level) {
+  const Model& M = c->model.M;
+  if (c->h.n_pending && !c->h.err) {
+    const u64 n = c->h.n_pending;
+    if (n > c->opt.pending_entries) return fail(VSRMC_E_REP, "more violating successors in the probed level than the pending list holds (pending_entries)");
+    u64* d_out = nullptr;
+    HIPCHK(hipMalloc((void**)&d_out, n * 16));
+    struct FreeOut { u64* p; ~FreeOut() { (void)hipFree(p); } } free_out{d_out};
+    u64 zero = 0, kept = 0;
+    HIPCHK(hipMemcpyAsync(c->d_find, &zero, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_probe_resolve<0>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, M, src_words, src_off, (const u64*)c->pending, n, (const Slot*)c->table,
+                       c->tmask, level, d_out, n, (unsigned long long*)c->d_find, c->ctl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    c->extra_launches++;
+    HIPCHK(hipMemcpyAsync(&kept, c->d_find, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->expand_ms += ms;
+    if (kept) HIPCHK(hipMemcpyAsync(c->pending, d_out, kept * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->ctl->n_pending, &kept, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->h, c->ctl, sizeof(c->h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return pass_verdict(c, level);
+}
+
 // One single-pass launch over an arbitrary source (a slice of the newest level, or the partial next frontier a MODE_REGEN
 // slice just wrote), unsharded.  Resets the level counters, returns them in c->h.  Destination = the next-frontier buffers.
 // io != nullptr: a pass of a sharded run (vsr_deep.hpp) — successors owned by other ranks are announced into io's buckets
@@ -908,6 +981,43 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
         probe_ccap = pcap;
         fs.kernel = c->probe_kernel; fs.ccap = pcap; fs.lds = dyn; fs.blocks_per_cu = (unsigned)(VSR_OCC + 1);
       }
+    }
+    // ... or, where the configuration has them, the probe pass's own kernels (vsr_probe_scan.hpp): under the same conditions
+    const bool use_scan = one_rank && mode == MODE_PROBE && c->probe_scan_kernel && !c->probe_scan_off && !c->saw_violation && !c->probe_all_actions && fs.tile == 64 &&
+                          !use_probe && p_offset == 0 && n_parents <= ((u64)1 << 40);
+    if (use_scan) {
+      const size_t dyn = pscan_lds_bytes(fs.stride);
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, c->probe_scan_kernel, VSR_BLOCK, dyn) != hipSuccess || nb < 1) return fail(VSRMC_E_HIP, "k_probe_scan: no resident block");
+      const u64 nmt = (n_parents + PSCAN_MT - 1) / PSCAN_MT;
+      const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((nmt + 3) / 4, (u64)c->num_cus * (u64)nb));
+      const u32 draw = nmt >= (u64)grid * 4 * PSCAN_DRAW * 4 ? (u32)PSCAN_DRAW : 1u;   // (a small pass draws single mini-tiles: every wave gets work)
+      HIPCHK(hipMemsetAsync(c->probe_list, 0, 8, c->stream));
+      HIPCHK(hipEventRecord(c->ev[0], c->stream));
+      hipLaunchKernelGGL((ProbeScanKernel)c->probe_scan_kernel, dim3(grid), dim3(VSR_BLOCK), dyn, c->stream, M, src_words, src_off, n_parents, c->ctl, fs.stride, draw,
+                         c->probe_list, c->probe_list_cap);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL((ProbeApplyKernel)c->probe_apply_kernel, dim3((unsigned)c->num_cus * 8), dim3(VSR_BLOCK), 0, c->stream, M, src_words, src_off,
+                         (const u64*)c->probe_list, c->probe_list_cap, c->pending, c->opt.pending_entries, c->ctl);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      c->extra_launches = 1;                                     // (the second kernel of the pass)
+      u64 listed = 0;
+      HIPCHK(hipMemcpyAsync(&listed, c->probe_list, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(&c->h, c->ctl, sizeof(c->h), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+      c->expand_ms += ms;
+      if (listed > c->probe_list_cap && !c->h.err) {             // more footprint instances than the list holds: nothing of this pass counts, the mode-capable k_expand runs it
+        const u64 before = c->extra_launches + 1;
+        c->probe_scan_off = true;
+        const int rrc = expand_pass(c, src_words, src_off, n_parents, p_offset, level, mode, src_max_bag, dst, io, claim_bits, claim_w);
+        c->probe_scan_off = false;
+        c->extra_launches += before;
+        return rrc;
+      }
+      return probe_pass_finish(c, src_words, src_off, level);
     }
     u32 cchunk = 0;
     if (io) {
@@ -988,34 +1098,8 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
     c->extra_launches += before;
     return rrc;
   }
-  if (use_probe && c->h.n_pending && !c->h.err) {              // the failing successors the probe-only pass wrote down: fingerprinted and looked up now (k_probe_resolve)
-    const u64 n = c->h.n_pending;
-    if (n > c->opt.pending_entries) return fail(VSRMC_E_REP, "more violating successors in the probed level than the pending list holds (pending_entries)");
-    u64* d_out = nullptr;
-    HIPCHK(hipMalloc((void**)&d_out, n * 16));
-    struct FreeOut { u64* p; ~FreeOut() { (void)hipFree(p); } } free_out{d_out};
-    u64 zero = 0, kept = 0;
-    HIPCHK(hipMemcpyAsync(c->d_find, &zero, 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_probe_resolve<0>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, M, src_words, src_off, (const u64*)c->pending, n, (const Slot*)c->table,
-                       c->tmask, level, d_out, n, (unsigned long long*)c->d_find, c->ctl);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&kept, c->d_find, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (kept) HIPCHK(hipMemcpyAsync(c->pending, d_out, kept * 16, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(&c->ctl->n_pending, &kept, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(&c->h, c->ctl, sizeof(c->h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  if (!c->h.err && c->h.full) {                                // a pass into buffers that ran out (LevelCtl::full): an error here — the caller sized the slice
-    c->h.err = ERR_FRONTIER_FULL;
-    c->h.err_info = c->h.full_info << 16;
-  }
-  if (c->h.err) return level_error(c, c->h, level);
-  if (c->h.ties) {
-    c->failed = 1;
-    return fail(VSRMC_E_STATE, "two successors of one level share a VIEW fingerprint but differ in the aux variables (SURVEY F2)");
-  }
-  return 0;
+  if (use_probe) return probe_pass_finish(c, src_words, src_off, level);
+  return pass_verdict(c, level);
 }
 
 // one step of a trace walk through the seen-set (k_table_lookup): by_low_bits = 0: the slot of fingerprint `key`; 1: the slot of

@@ -21,6 +21,7 @@
 #include "vsr_parse.hpp"
 #include "vras_parse.hpp"
 #include "vsr_kernels.hpp"
+#include "vsr_probe_scan.hpp"
 #include "vsr_terminal.hpp"
 
 #define VSRMC_FP_VERSION 2          // fingerprint function of this build; checkpoints of another version are refused
