@@ -288,6 +288,45 @@ typedef struct vsrmc_terminal_info {
 int32_t vsrmc_checker_terminal_scan(vsrmc_checker* c, vsrmc_terminal_info* out);
 int32_t vsrmc_checker_terminal_states(vsrmc_checker* c, uint64_t* fps, uint8_t* flags, uint64_t cap, uint64_t* n);
 
+/* ---- state predicates: user-written invariants and reachability queries (VSR.tla only) -----------------------------------------
+ * A closed expression language over the lowered record, written in TLA+ syntax — the language, what is refused and where an evaluation
+ * departs from TLC (accesses outside a domain have a defined result; model-value literals are refused under SYMMETRY; the aux variables are seen
+ * through the representative the search keeps) are specified in csrc/vsr_where_parse.hpp.  The text holds one expression or definitions
+ * `Name == expr`; every definition not written `LOCAL Name == expr` is exported, at most 8; exported predicate k is bit k everywhere below.
+ * vsrmc_where_compile: needs no device.  VSRMC_E_ARG with "line:col: reason" in vsrmc_last_error() for a text that is refused (models 2 and 3:
+ *   "state predicates: VSR.tla only"), VSRMC_E_REP for a program beyond 4096 ops or an operand depth beyond 32.
+ * vsrmc_where_batch: n wire records of the caller (the layout of vsrmc_terminal_batch); flags[i] = the bits of record i.
+ * vsrmc_checker_where_scan: k_where (csrc/vsr_where.hpp) over the newest STORED level.  Valid exactly where vsrmc_checker_terminal_scan is
+ *   (VSRMC_E_STATE on a sharded checker, on seen-set-only levels, after a failed search), any number of times; changes nothing a later call
+ *   can observe.  count / min_fp are exact.  The witness of predicate k is vsrmc_checker_trace_fp(c, level, min_fp[k], ...): with levels scanned
+ *   shallowest first it is a shortest behaviour into a state that satisfies k, and the same one in every run.
+ * vsrmc_checker_where_states: the records of the last scan with any bit set, fingerprints ascending, their bits beside them; fps == NULL asks
+ *   for the number.  The contract of vsrmc_checker_terminal_states: at most 2^20 are kept, beyond that *n is the true number and the call
+ *   returns VSRMC_E_REP.  (Test knob: the environment variable VSRMC_WHERE_LIST_CAP=N lowers the 2^20 to N; it has no other use.)
+ * The compute calls fail with VSRMC_E_HIP without a device: there is no CPU evaluation. */
+typedef struct vsrmc_where vsrmc_where;
+typedef struct vsrmc_where_desc {
+  int32_t n_names;                                 /* exported predicates */
+  int32_t n_ops, depth;                            /* program length (the final END included), operand-stack depth */
+  int32_t msg_loops;                               /* nesting of the quantifiers over DOMAIN messages that remain as loops: 0, 1 or 2 */
+  int32_t n_bodies;                                /* quantifier bodies after unfolding (\E r1, r2 \in replicas at ReplicaCount 3: 9) */
+  int32_t reserved0;
+  char names[8][64];
+} vsrmc_where_desc;
+typedef struct vsrmc_where_info {
+  int32_t level, reserved0;                        /* the level scanned = the newest STORED level */
+  uint64_t n_states;
+  uint64_t count[8];                               /* records that satisfy predicate k */
+  uint64_t min_fp[8], min_index[8];                /* the smallest fingerprint among them and its index in the level; ~0 if none */
+  double kernel_ms;                                /* HIP-event time of k_where */
+} vsrmc_where_info;
+int32_t vsrmc_where_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
+void vsrmc_where_destroy(vsrmc_where* w);
+int32_t vsrmc_where_describe(const vsrmc_where* w, vsrmc_where_desc* out);
+int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint8_t* flags);
+int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_where_info* out);
+int32_t vsrmc_checker_where_states(vsrmc_checker* c, uint64_t* fps, uint8_t* bits, uint64_t cap, uint64_t* n);
+
 /* Probe level: expand the newest level without storing its successors — invariants are evaluated on every successor that is
  * not a state of an earlier level, nothing is inserted or written, so the level costs no frontier memory; the search cannot
  * continue afterwards.  Finds a violation one level beyond what memory can hold.  Also valid right after a step that failed

@@ -5,4 +5,4 @@ mirror of the TLC interfaces the path replaces), sharded.py (multi-GPU level loo
 `vsr-tlaplus_amd` at the repo root is a symbolic link to this directory (the name the task layout uses; a dash is not importable).
 """
 from .capi import VsrmcError, load  # noqa: F401
-from .checker import ACTION_NAMES, FPSet, Model, ModelChecker, StateQueue  # noqa: F401
+from .checker import ACTION_NAMES, FPSet, Model, ModelChecker, StateQueue, Where  # noqa: F401

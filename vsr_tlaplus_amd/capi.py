@@ -46,6 +46,16 @@ class TerminalInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved0"}
 
 
+class WhereDesc(C.Structure):
+    _fields_ = [("n_names", C.c_int32), ("n_ops", C.c_int32), ("depth", C.c_int32), ("msg_loops", C.c_int32), ("n_bodies", C.c_int32),
+                ("reserved0", C.c_int32), ("names", (C.c_char * 64) * 8)]
+
+
+class WhereInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8),
+                ("min_index", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
+
+
 class ShardIO(C.Structure):
     _fields_ = [("cand_send", C.c_void_p), ("cand_cap", C.c_uint64)]
 
@@ -119,6 +129,12 @@ SYMBOLS = {
     "vsrmc_terminal_batch": (C.c_int32, [V, C.c_int32, V, V, C.c_uint64, V]),
     "vsrmc_checker_terminal_scan": (C.c_int32, [V, C.POINTER(TerminalInfo)]),
     "vsrmc_checker_terminal_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_where_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
+    "vsrmc_where_destroy": (None, [V]),
+    "vsrmc_where_describe": (C.c_int32, [V, C.POINTER(WhereDesc)]),
+    "vsrmc_where_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V]),
+    "vsrmc_checker_where_scan": (C.c_int32, [V, V, C.POINTER(WhereInfo)]),
+    "vsrmc_checker_where_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_check": (C.c_int32, [V, C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(LevelInfo)]),
     "vsrmc_queue_create": (C.c_int32, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(V)]),
     "vsrmc_queue_enqueue_batch": (C.c_int32, [V, V, V, C.c_uint64]),

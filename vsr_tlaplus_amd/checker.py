@@ -27,6 +27,33 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+class Where:
+    """State predicates compiled for one model (Model.compile_where): `names[k]` is the exported predicate of bit k."""
+
+    def __init__(self, handle, model):
+        self._h = handle
+        self.model = model                                            # (keeps the model alive)
+        self.names = self.describe()["names"]
+
+    def describe(self):
+        """-> dict(names, n_ops, depth, msg_loops, n_bodies): the exported names, program length, operand-stack depth, nesting of the message
+        quantifiers that remain as loops, quantifier bodies after unfolding."""
+        d = capi.WhereDesc()
+        check(capi.load().vsrmc_where_describe(self._h, C.byref(d)))
+        return dict(names=[d.names[k].value.decode() for k in range(d.n_names)], n_ops=d.n_ops, depth=d.depth, msg_loops=d.msg_loops, n_bodies=d.n_bodies)
+
+    def close(self):
+        if self._h:
+            capi.load().vsrmc_where_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Model:
     """The lowered (VSR.tla, VSR.cfg) pair."""
 
@@ -131,6 +158,22 @@ class Model:
         n = len(off) - 1
         flags = np.zeros(max(1, n), dtype=np.uint8)
         check(capi.load().vsrmc_terminal_batch(self._h, device, _p(words), _p(off), n, _p(flags)))
+        return flags[:n]
+
+    def compile_where(self, text):
+        """State predicates (csrc/vsr_where_parse.hpp: one expression or `Name == expr` definitions in TLA+ syntax) -> Where.  Needs no device.
+        Raises VsrmcError with "line:col: reason" for a text that is refused."""
+        h = C.c_void_p()
+        check(capi.load().vsrmc_where_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return Where(h, self)
+
+    def where_flags(self, w, words, off, device=0):
+        """One byte per state of a batch (k_where): bit k = exported predicate k of `w` holds."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        flags = np.zeros(max(1, n), dtype=np.uint8)
+        check(capi.load().vsrmc_where_batch(self._h, device, w._h, _p(words), _p(off), n, _p(flags)))
         return flags[:n]
 
     def tlc_fingerprints(self, words, off, device=0):
@@ -352,6 +395,7 @@ class ModelChecker:
             self.violation = None
             self.rebased = []
             self.deadlock = None
+            self.witness = None
             self.depth = self.level + info.reserved0               # a deep search: the levels beyond the stored one came along in the seen-set
         check(capi.load().vsrmc_checker_options(self._h, C.byref(o)))       # sizes left 0 were derived from the free device memory
 
@@ -368,6 +412,7 @@ class ModelChecker:
         self.violation = None
         self.rebased = []
         self.deadlock = None
+        self.witness = None
 
     def reset(self):
         """Back to Init with an empty seen-set; keeps the HBM allocations (a fresh TLC run on the same model)."""
@@ -467,11 +512,14 @@ class ModelChecker:
             check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))
         return st.value
 
-    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False):
+    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False, reach=None, never=None):
         """Worker.run until the queue is empty, an invariant is violated, or a bound is hit — the automatic level scheme: levels are
         stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen).
         check_deadlock (TLC's default, off here): every stored level is scanned for terminal states before it is expanded; the first level
-        that has one ends the run with "deadlock" — self.deadlock = the scan's result, deadlock_trace() the behaviour."""
+        that has one ends the run with "deadlock" — self.deadlock = the scan's result, deadlock_trace() the behaviour.
+        reach / never (a Where each, off by default): every stored level is scanned (k_where) before it is expanded, where check_deadlock scans.  The
+        first level with a state that satisfies a predicate of `reach` ends the run with "reached"; one that satisfies a predicate of `never` (the
+        negation of a user's invariant) ends it with "violation".  self.witness = dict(level, k, name, fp, index, kind); witness_trace() the behaviour."""
         import time
         t0 = time.time()
         while True:
@@ -485,6 +533,16 @@ class ModelChecker:
                 t = self.terminal_scan()
                 if t["n_terminal"]:
                     return "deadlock"
+            if self.depth == self.level and self.n_frontier:
+                for w, kind in ((never, "violation"), (reach, "reached")):
+                    if w is None:
+                        continue
+                    t = self.where_scan(w)
+                    hits = [k for k in range(len(w.names)) if t["count"][k]]
+                    if hits:
+                        k = hits[0]
+                        self.witness = dict(level=t["level"], k=k, name=w.names[k], fp=t["min_fp"][k], index=t["min_index"][k], kind=kind)
+                        return kind
             kind, d, p = self.advance()
             if d["n_new"] == 0:
                 return "exhausted"
@@ -522,6 +580,45 @@ class ModelChecker:
         flags = np.zeros(max(1, n.value), dtype=np.uint8)
         check(lib.vsrmc_checker_terminal_states(self._h, _p(fps), _p(flags), len(fps), C.byref(n)))
         return fps[: n.value].copy(), flags[: n.value].copy()
+
+    def where_scan(self, w):
+        """Evaluate the predicates of `w` on the newest stored level (k_where; nothing applied, the seen-set untouched) -> dict(level, n_states,
+        count[k], min_fp[k], min_index[k], kernel_ms), one entry per exported predicate; fingerprint / index None where no state satisfies it."""
+        info = capi.WhereInfo()
+        check(capi.load().vsrmc_checker_where_scan(self._h, w._h, C.byref(info)))
+        none = (1 << 64) - 1
+        n = len(w.names)
+        self._where = (w, info.level, [None if info.min_fp[k] == none else int(info.min_fp[k]) for k in range(n)])
+        return dict(level=info.level, n_states=info.n_states, count=[int(info.count[k]) for k in range(n)], min_fp=list(self._where[2]),
+                    min_index=[None if info.min_index[k] == none else int(info.min_index[k]) for k in range(n)], kernel_ms=info.kernel_ms)
+
+    def where_states(self):
+        """The states of the last where_scan() that satisfy any predicate -> (fingerprints ascending, their bits)."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_where_states(self._h, None, None, 0, C.byref(n))
+        if rc not in (0, -5):                                             # -5 (VSRMC_E_REP): more than the list holds — raised below, by the call that copies
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        bits = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_where_states(self._h, _p(fps), _p(bits), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), bits[: n.value].copy()
+
+    def witness_trace(self, k=None):
+        """The behaviour from Init into the state with the smallest fingerprint that satisfies predicate k (a number or a name) in the level of the
+        last where_scan(); k=None: the witness run(reach= / never=) stopped at.  [(action name, record)], the shape of violation_trace()."""
+        if k is None:
+            if self.witness is None:
+                raise ValueError("run(reach=..) / run(never=..) has not stopped at a state")
+            return self.trace_fp(self.witness["level"], self.witness["fp"])
+        w, level, fps = getattr(self, "_where", (None, None, None))
+        if w is None:
+            raise ValueError("no where_scan() yet")
+        if not isinstance(k, int):
+            k = w.names.index(k)
+        if fps[k] is None:
+            raise ValueError("no state of level %d satisfies %s" % (level, w.names[k]))
+        return self.trace_fp(level, fps[k])
 
     def deadlock_trace(self):
         """The behaviour into the terminal state terminal_scan() / run(check_deadlock=True) reported (self.deadlock): [(action name, record)]

@@ -110,6 +110,11 @@ struct vsrmc_checker {
   std::vector<uint8_t> term_flags;
   u64 term_total = 0;
   int term_level = -1;
+  // the last vsrmc_checker_where_scan (host_where.hpp): the same for the records with any predicate bit set
+  std::vector<u64> where_fps;
+  std::vector<uint8_t> where_bits;
+  u64 where_total = 0;
+  int where_level = -1;
 #ifdef VSRMC_TEST_HOOKS
   // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
   std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending

@@ -1,0 +1,219 @@
+// vsr_where.hpp — k_where: user-written state predicates (vsr_where_parse.hpp compiles them) evaluated on every record of a level.  A streaming scan
+// with the shape of k_terminal (vsr_terminal.hpp): one lane per record, straight from global memory, grid-stride over whole waves,
+// refs[i] == 0 = a hole.  It reads records only: nothing is applied, the seen-set is not touched, k_expand / k_terminal / k_select are not involved.
+//
+// The program is a straight-line postfix sequence of 32-bit ops (opcode << 24 | argument), the same for every lane: quantifiers over replicas, clients,
+// Values, ranges and log indices were unfolded by the compiler, only quantifiers over DOMAIN messages remain as loops (W_MBEGIN .. W_MEND, at most two
+// nested).  Ops are read at a wave-uniform address (scalar loads), dispatch is a uniform branch.  The operand stack lives in LDS, laid out
+// [slot][lane] in 32-bit words: the stack pointer is uniform, so the 64 lanes of a wave touch 64 consecutive words — no bank conflict — and no
+// runtime-indexed private array exists that would go to scratch.  A message loop runs to the wave's largest nmsg; a lane past its own bag does not fold
+// its body value into the accumulator (it contributes the quantifier's neutral element).
+//
+// Output per exported predicate k < 8: bit k of an optional flag byte per record, an exact counter (wave ballots summed in scalar registers, one atomic
+// per wave at the end), the smallest fingerprint that satisfies it (wave reduction, one atomicMin per wave with a hit) and, for records with any bit
+// set, a (fingerprint, index, bits) triple appended wave-wise to a list of which the first list_cap that arrive are kept (WhereCtl::n_list = true number).
+#pragma once
+#include "vsr_model.hpp"
+
+namespace vsr {
+
+enum {
+  W_END = 0,
+  W_PUSH,      // arg: 24-bit signed immediate
+  W_LDBITS,    // arg: word(8) | shift(6) << 8 | width(6) << 14 : (rec[word] >> shift) & mask
+  W_LDM,       // arg: loop(1) | shift(6) << 1 | width(6) << 7 : the same of the current bag word of message loop `loop`
+  W_LDMENT,    // arg: loop : m.message — the entry byte of a PrepareMsg, 0 for every other type
+  W_ENTF,      // arg: 0 view_number, 1 operation (value index + 1), 2 client_id, 3 request_number : field of the entry byte on top; an absent entry (0) reads 0
+  W_LOGLEN,    // number of entries of the 24-bit log on top
+  W_POPC,
+  W_ADD, W_SUB, W_DIV,
+  W_EQ, W_NE, W_LT, W_LE, W_GT, W_GE,
+  W_AND, W_OR, W_NOT, W_IMP,
+  W_SEL,       // pops a, c, acc; pushes c ? a : acc
+  W_MBEGIN,    // arg: pc of the matching W_MEND (12) | loop << 12 | forall << 13
+  W_MEND,      // arg: loop | forall << 1 | pc of the first body op << 2
+  W_OUT,       // arg: k : pops a boolean into bit k of the result
+  W_OPCOUNT
+};
+enum { WHERE_MAX_OPS = 4096, WHERE_MAX_DEPTH = 32, WHERE_MAX_EXPORTS = 8 };
+
+VSR_HD u32 w_op(int code, u32 arg) { return ((u32)code << 24) | (arg & 0xFFFFFFu); }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VSR_WHERE_UNI(x) ((u32)__builtin_amdgcn_readfirstlane((int)(x)))
+#else
+#define VSR_WHERE_UNI(x) (x)
+#endif
+
+// One record through the program.  `S` is the operand stack (S[slot] -> int&); valid = the lane has a record; wmax = the largest nmsg of the lanes that
+// run together (on the host: nmsg).  Returns the exported bits.
+template <typename STACK, typename PTR>
+VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool valid, int nmsg, int wmax, STACK& S) {
+  u32 bits = 0;
+  int sp = 0, pc = 0;
+  int j0 = 0, j1 = 0, acc0 = 0, acc1 = 0;
+  u64 mw0 = 0, mw1 = 0;
+  for (;;) {
+    const u32 op = VSR_WHERE_UNI(prog[pc]);
+    pc++;
+    const u32 arg = op & 0xFFFFFFu;
+    switch (op >> 24) {
+      case W_END: return bits;
+      case W_PUSH: S[sp++] = (int)(arg << 8) >> 8; break;
+      case W_LDBITS: {
+        const u64 w = valid ? rec[arg & 0xFF] : (u64)0;
+        S[sp++] = (int)((u32)(w >> ((arg >> 8) & 63)) & (u32)((((u64)1) << ((arg >> 14) & 63)) - 1));
+        break;
+      }
+      case W_LDM: {
+        const u64 w = (arg & 1) ? mw1 : mw0;
+        S[sp++] = (int)((u32)(w >> ((arg >> 1) & 63)) & (u32)((((u64)1) << ((arg >> 7) & 63)) - 1));
+        break;
+      }
+      case W_LDMENT: {
+        const u64 w = (arg & 1) ? mw1 : mw0;
+        S[sp++] = m_type(w) == T_PREPARE ? (int)(m_lg(w) & 0xFF) : 0;
+        break;
+      }
+      case W_ENTF: {
+        const int b = S[sp - 1];
+        const int f = arg == 0 ? (b & 7) : arg == 1 ? entry_val(b) + 1 : arg == 2 ? entry_client(b) : entry_req(b);
+        S[sp - 1] = b ? f : 0;
+        break;
+      }
+      case W_LOGLEN: S[sp - 1] = log_len((u32)S[sp - 1]); break;
+      case W_POPC: {
+        u32 x = (u32)S[sp - 1];
+        int n = 0;
+        for (int k = 0; k < 8; k++) n += (int)((x >> k) & 1);
+        S[sp - 1] = n;
+        break;
+      }
+      case W_NOT: S[sp - 1] = S[sp - 1] ? 0 : 1; break;
+      case W_SEL: {
+        const int a = S[sp - 1], c = S[sp - 2], acc = S[sp - 3];
+        sp -= 2;
+        S[sp - 1] = c ? a : acc;
+        break;
+      }
+      case W_MBEGIN: {
+        const int forall = (int)((arg >> 13) & 1);
+        if ((arg >> 12) & 1) { j1 = 0; acc1 = forall; mw1 = (valid && nmsg > 0) ? rec[fixed] : (u64)0; }
+        else { j0 = 0; acc0 = forall; mw0 = (valid && nmsg > 0) ? rec[fixed] : (u64)0; }
+        if (wmax == 0) { S[sp++] = forall; pc = (int)(arg & 0xFFF) + 1; }
+        break;
+      }
+      case W_MEND: {
+        const int forall = (int)((arg >> 1) & 1);
+        const int v = S[--sp];
+        if (arg & 1) {
+          if (j1 < nmsg) acc1 = forall ? (acc1 & v) : (acc1 | v);
+          j1++;
+          if (j1 < wmax) { mw1 = (valid && j1 < nmsg) ? rec[fixed + j1] : (u64)0; pc = (int)(arg >> 2); }
+          else S[sp++] = acc1;
+        } else {
+          if (j0 < nmsg) acc0 = forall ? (acc0 & v) : (acc0 | v);
+          j0++;
+          if (j0 < wmax) { mw0 = (valid && j0 < nmsg) ? rec[fixed + j0] : (u64)0; pc = (int)(arg >> 2); }
+          else S[sp++] = acc0;
+        }
+        break;
+      }
+      case W_OUT: bits |= (S[--sp] ? 1u : 0u) << (arg & 7); break;
+      default: {                                                    // the binary operators
+        const int b = S[--sp], a = S[sp - 1];
+        int r = 0;
+        switch (op >> 24) {
+          case W_ADD: r = a + b; break;
+          case W_SUB: r = a - b; break;
+          case W_DIV: {                                             // TLA+'s \div rounds towards minus infinity; a zero divisor gives 0
+            if (b != 0) { r = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) r--; }
+            break;
+          }
+          case W_EQ: r = a == b; break;
+          case W_NE: r = a != b; break;
+          case W_LT: r = a < b; break;
+          case W_LE: r = a <= b; break;
+          case W_GT: r = a > b; break;
+          case W_GE: r = a >= b; break;
+          case W_AND: r = (a != 0) & (b != 0); break;
+          case W_OR: r = (a != 0) | (b != 0); break;
+          case W_IMP: r = (a == 0) | (b != 0); break;
+        }
+        S[sp - 1] = r;
+      }
+    }
+  }
+}
+
+#if defined(__HIPCC__)
+
+struct WhereCtl {
+  u64 scanned;                        // records looked at (holes excluded)
+  u64 count[WHERE_MAX_EXPORTS];       // records that satisfy predicate k
+  u64 min_fp[WHERE_MAX_EXPORTS];      // the smallest fingerprint among them, ~0 = none
+  u64 n_list;                         // records with any bit set offered to the list
+};
+
+struct WhereLdsStack {                // [slot][lane of the block]
+  int* base;
+  __device__ __forceinline__ int& operator[](int slot) const { return base[slot * 256]; }
+};
+
+__global__ void __launch_bounds__(256)
+k_where(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restrict__ words, const u64* __restrict__ refs, const u64* __restrict__ fps,
+        u64 n, uint8_t* flags, WhereCtl* ctl, u64* list, u64 list_cap) {
+  __shared__ int stack[WHERE_MAX_DEPTH * 256];
+  WhereLdsStack S{stack + threadIdx.x};
+  u32 cnt[WHERE_MAX_EXPORTS];                                      // wave-uniform (ballot popcounts); indexed by unrolled constants only
+#pragma unroll
+  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) cnt[k] = 0;
+  u32 n_scanned = 0;
+  const u64 step = (u64)gridDim.x * blockDim.x;
+  const u64 n_round = (n + 63) & ~(u64)63;                         // whole waves stay together
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += step) {
+    const u64 ref = i < n ? refs[i] : 0;
+    const bool valid = ref != 0;
+    const u64* rec = words + (ref >> 8);
+    const int nmsg = valid ? hdr_nmsg(rec[0]) : 0;
+    int wmax = nmsg;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
+    wmax = (int)VSR_WHERE_UNI(wmax);
+    const u32 raw = where_run(prog, M.fixed, rec, valid, nmsg, wmax, S);
+    const u32 bits = valid ? raw : 0;                              // (a lane without a record ran the program over zeros: TRUE would count it)
+    if (valid && flags) flags[i] = (uint8_t)bits;
+    n_scanned += (u32)__popcll(__ballot(valid));
+    if (__ballot(bits != 0) == 0) continue;                        // (wave-uniform)
+#pragma unroll
+    for (int k = 0; k < WHERE_MAX_EXPORTS; k++) {
+      if (k >= n_exports) break;
+      const bool hit = (bits >> k) & 1;
+      const u64 b = __ballot(hit);
+      if (b == 0) continue;
+      cnt[k] += (u32)__popcll(b);
+      if (fps) {
+        const u64 m = term_wave_min(hit ? fps[i] : ~(u64)0);
+        if (lane_id() == 0) atomicMin((unsigned long long*)&ctl->min_fp[k], (unsigned long long)m);
+      }
+    }
+    if (fps && list && bits != 0) {
+      const u64 k = wave_alloc(&ctl->n_list);
+      if (k < list_cap) {
+        list[3 * k] = fps[i];
+        list[3 * k + 1] = i;
+        list[3 * k + 2] = (u64)bits;
+      }
+    }
+  }
+  if (lane_id() == 0) {                                            // one atomic per counter and wave
+    if (n_scanned) atomicAdd((unsigned long long*)&ctl->scanned, (unsigned long long)n_scanned);
+#pragma unroll
+    for (int k = 0; k < WHERE_MAX_EXPORTS; k++)
+      if (cnt[k]) atomicAdd((unsigned long long*)&ctl->count[k], (unsigned long long)cnt[k]);
+  }
+}
+
+#endif  // __HIPCC__
+
+}  // namespace vsr

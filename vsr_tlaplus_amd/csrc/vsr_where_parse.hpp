@@ -1,0 +1,750 @@
+// vsr_where_parse.hpp — state predicates: a closed expression language over the lowered VSR.tla record, written in TLA+ syntax, compiled on the host
+// into the postfix program k_where runs (vsr_where.hpp).  General TLA+ evaluation stays out of scope: this is what a user needs to ask
+// "is a state with property P reachable" / "does P hold in every state" about the state variables the record stores.
+//
+// Input: one expression, or definitions `Name == expr`.  `\*` and `(* *)` comments.  A later definition may use an earlier name (inlined).  Every
+// definition is exported (at most 8) unless it is written `LOCAL Name == expr`; a lone expression is exported under the name "where".
+//
+//   boolean     TRUE FALSE /\ \/ ~ => <=> ( )      precedence as in TLA+: => < <=> < /\,\/ < ~ < comparisons < .. < +,- < \div < application.
+//               /\ and \/ may not be mixed without parentheses (SANY refuses that too).  No indentation-sensitive bullet lists.
+//   integer     literals + - \div  ReplicaCount ClientCount StartViewOnTimerLimit Cardinality(Values)
+//   comparison  = # /= < <= =< > >=  ; = and # also between statuses, message types, values, booleans and log entries (the whole record)
+//   quantifier  \A x, y \in S : e   \E ...   with S = replicas | clients | Values | a..b (constant bounds) | DOMAIN rep_log[r] | DOMAIN messages
+//               (at most two nested quantifiers over DOMAIN messages); x \in S with the first five as a test
+//   state       rep_status[r] rep_view_number[r] rep_op_number[r] rep_commit_number[r] rep_last_normal_view[r] rep_sent_dvc[r] rep_sent_sv[r]
+//               rep_peer_op_number[r][p]   rep_client_table[r][c].request_number / .op_number / .executed
+//               Len(rep_log[r])   rep_log[r][i] and its fields .view_number .operation .client_id .request_number
+//               Cardinality(rep_svc_recv[r])   Cardinality(rep_dvc_recv[r])
+//               aux_svc   aux_client_acked[v]   v \in DOMAIN aux_client_acked
+//               for m bound over DOMAIN messages: m.type .view_number .dest .source .op_number .commit_number .last_normal_vn .first_op,
+//               m.message and its entry fields, messages[m] (the delivery count; keys with count 0 stay in the bag and are visited)
+//   constants   Normal ViewChange Recovering, the message-type names, Nil, and — without SYMMETRY — the model values of Values
+// An index may be any integer expression (rep_view_number[m.dest]): it becomes a select chain over the R (or C, or |Values|) candidates.
+//
+// WHERE THIS DEPARTS FROM TLC
+//   * TLC raises an evaluation error for an access outside a domain.  Here such an access has a defined result: an absent log entry or message field
+//     reads 0 (an absent entry's .operation equals no value and equals Nil; m.message of anything but a PrepareMsg is the absent entry);
+//     aux_client_acked[v] outside its domain is FALSE; a replica or client index out of range yields -1, which equals no constant (FALSE where the
+//     field is a boolean).  \div by zero gives 0.
+//   * A model-value literal (v1) is refused when the model was loaded with SYMMETRY: values then enter only through bound variables, every predicate
+//     is symmetric, and a hit does not depend on which member of its orbit the search stored.
+//   * aux_svc and aux_client_acked are outside VIEW: of the states that differ only there the search keeps one representative (the smallest canonical
+//     auxkey), and a predicate on them sees that representative.
+//
+// Refused (code 1 = VSRMC_E_ARG, message "line:col: reason"): unknown identifier, unbound variable, forward or recursive reference, type mismatch
+// (rep_status[r] = 1), primes, temporal operators, CHOOSE, LAMBDA, set constructors, a quantifier over any other set, more than 8 exported names.
+// Code 2 = VSRMC_E_REP: a program beyond 4096 ops or an operand depth beyond 32.
+#pragma once
+#include <algorithm>
+#include <cctype>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "vsr_where.hpp"
+
+namespace vsr {
+
+struct WhereProgram {
+  std::vector<u32> ops;
+  std::vector<std::string> names;      // exported, bit k = names[k]
+  int depth = 0, msg_loops = 0, n_bodies = 0;
+};
+
+namespace where_detail {
+
+struct Err { int code; std::string msg; };
+enum { TK_EOF, TK_ID, TK_NUM, TK_OP };
+struct Tok { int kind; std::string s; long v; int line, col; };
+enum { TY_INT, TY_BOOL, TY_STATUS, TY_MTYPE, TY_VALUE, TY_ENTRY };
+enum { N_NUM, N_BOOL, N_ID, N_NOT, N_NEG, N_BIN, N_QUANT, N_INDEX, N_FIELD, N_CALL, N_DOMAIN };
+struct Node;
+typedef std::shared_ptr<Node> NodeP;
+struct Node {
+  int k = 0;
+  std::string s;
+  long v = 0;
+  int line = 0, col = 0;
+  bool paren = false;
+  std::vector<NodeP> c;
+  std::vector<std::string> vars;
+};
+
+[[noreturn]] inline void fail_at(int line, int col, const std::string& why, int code = 1) {
+  throw Err{code, std::to_string(line) + ":" + std::to_string(col) + ": " + why};
+}
+inline const char* type_name(int t) {
+  static const char* const N[] = {"an integer", "a boolean", "a status", "a message type", "a value", "a log entry"};
+  return N[t];
+}
+
+inline std::vector<Tok> lex(const std::string& t) {
+  std::vector<Tok> out;
+  size_t i = 0;
+  int line = 1, col = 1;
+  auto adv = [&](size_t n) { for (size_t k = 0; k < n && i < t.size(); k++, i++) { if (t[i] == '\n') { line++; col = 1; } else col++; } };
+  static const char* const OPS[] = {"<=>", "|->", "\\/", "/\\", "=>", "==", "=<", "<=", ">=", "/=", "..", "[]", "<>", "~>", "<<", ">>", "=", "#", "<", ">",
+                                    "+", "-", "~", "(", ")", "[", "]", "{", "}", ",", ":", ".", "'", "*", "|", "@", "!", "%", "&", "^", "$", "?", ";"};
+  while (i < t.size()) {
+    const char ch = t[i];
+    if (ch == ' ' || ch == '\t' || ch == '\r' || ch == '\n') { adv(1); continue; }
+    if (t.compare(i, 2, "\\*") == 0) { while (i < t.size() && t[i] != '\n') adv(1); continue; }
+    if (t.compare(i, 2, "(*") == 0) {
+      const int l0 = line, c0 = col;
+      int depth = 0;
+      for (;;) {
+        if (i >= t.size()) fail_at(l0, c0, "comment is not closed");
+        if (t.compare(i, 2, "(*") == 0) { depth++; adv(2); }
+        else if (t.compare(i, 2, "*)") == 0) { depth--; adv(2); if (!depth) break; }
+        else adv(1);
+      }
+      continue;
+    }
+    Tok k{TK_OP, "", 0, line, col};
+    if (std::isdigit((unsigned char)ch)) {
+      size_t j = i;
+      while (j < t.size() && std::isdigit((unsigned char)t[j])) j++;
+      if (j - i > 6) fail_at(line, col, "integer literal too large");
+      k.kind = TK_NUM; k.s = t.substr(i, j - i); k.v = std::stol(k.s);
+      adv(j - i);
+    } else if (std::isalpha((unsigned char)ch) || ch == '_') {
+      size_t j = i;
+      while (j < t.size() && (std::isalnum((unsigned char)t[j]) || t[j] == '_')) j++;
+      k.kind = TK_ID; k.s = t.substr(i, j - i);
+      adv(j - i);
+    } else if (ch == '\\' && i + 1 < t.size() && std::isalpha((unsigned char)t[i + 1])) {
+      size_t j = i + 1;
+      while (j < t.size() && std::isalpha((unsigned char)t[j])) j++;
+      k.s = t.substr(i, j - i);
+      if (k.s == "\\land") k.s = "/\\";
+      else if (k.s == "\\lor") k.s = "\\/";
+      else if (k.s == "\\lnot" || k.s == "\\neg") k.s = "~";
+      else if (k.s == "\\leq") k.s = "<=";
+      else if (k.s == "\\geq") k.s = ">=";
+      else if (k.s == "\\equiv") k.s = "<=>";
+      adv(j - i);
+    } else {
+      bool found = false;
+      for (const char* o : OPS) {
+        const size_t n = std::strlen(o);
+        if (t.compare(i, n, o) == 0) { k.s = o; adv(n); found = true; break; }
+      }
+      if (!found) fail_at(line, col, std::string("unexpected character '") + ch + "'");
+    }
+    out.push_back(k);
+  }
+  out.push_back(Tok{TK_EOF, "", 0, line, col});
+  return out;
+}
+
+struct Parser {
+  std::vector<Tok> t;
+  size_t p = 0;
+  const Tok& peek(size_t a = 0) const { return t[std::min(p + a, t.size() - 1)]; }
+  bool is_op(const char* s, size_t a = 0) const { return peek(a).kind == TK_OP && peek(a).s == s; }
+  bool is_id(const char* s) const { return peek().kind == TK_ID && peek().s == s; }
+  [[noreturn]] void fail(const Tok& k, const std::string& why) const { fail_at(k.line, k.col, why); }
+  void expect(const char* s) {
+    if (!is_op(s)) fail(peek(), std::string("expected '") + s + "'" + (peek().kind == TK_EOF ? " before the end of the text" : " before '" + peek().s + "'"));
+    p++;
+  }
+  NodeP mk(int k, const Tok& at) { NodeP n = std::make_shared<Node>(); n->k = k; n->line = at.line; n->col = at.col; return n; }
+
+  static int binprec(const Tok& k) {
+    if (k.kind != TK_OP) return 0;
+    const std::string& s = k.s;
+    if (s == "=>") return 1;
+    if (s == "<=>") return 2;
+    if (s == "/\\" || s == "\\/") return 3;
+    if (s == "=" || s == "#" || s == "/=" || s == "<" || s == "<=" || s == "=<" || s == ">" || s == ">=" || s == "\\in") return 5;
+    if (s == "..") return 9;
+    if (s == "+" || s == "-") return 10;
+    if (s == "\\div") return 13;
+    return 0;
+  }
+  void refuse_unsupported(const Tok& k) const {
+    if (k.kind == TK_OP) {
+      const std::string& s = k.s;
+      if (s == "'") fail(k, "primed variables are not part of a state predicate");
+      if (s == "[]" || s == "<>" || s == "~>") fail(k, "temporal operators are not part of a state predicate");
+      if (s == "{" || s == "<<" || s == "|->" || s == "\\cup" || s == "\\cap" || s == "\\union" || s == "\\intersect" || s == "\\subseteq" || s == "\\X" || s == "\\times")
+        fail(k, "set, tuple and record constructors are not supported");
+      if (s == "\\notin") fail(k, "\\notin is not supported: write ~(x \\in S)");
+    } else if (k.kind == TK_ID) {
+      const std::string& s = k.s;
+      if (s == "CHOOSE" || s == "LAMBDA") fail(k, s + " is not supported");
+      if (s == "ENABLED" || s == "UNCHANGED" || s == "WF_vars" || s == "SF_vars") fail(k, s + ": action and temporal operators are not part of a state predicate");
+      if (s == "IF" || s == "THEN" || s == "ELSE" || s == "LET" || s == "IN" || s == "CASE" || s == "SUBSET" || s == "UNION" || s == "EXCEPT") fail(k, s + " is not supported");
+    }
+  }
+
+  NodeP expr(int minprec) {
+    NodeP lhs = unary();
+    for (;;) {
+      const Tok op = peek();
+      refuse_unsupported(op);
+      const int pr = binprec(op);
+      if (pr == 0 || pr < minprec) return lhs;
+      p++;
+      if (pr == 3 && lhs->k == N_BIN && !lhs->paren && (lhs->s == "/\\" || lhs->s == "\\/") && lhs->s != op.s)
+        fail(op, "/\\ and \\/ are mixed without parentheses");
+      NodeP rhs = op.s == "=>" ? expr(pr) : expr(pr + 1);          // => groups to the right, the others to the left
+      NodeP n = mk(N_BIN, op);
+      n->s = op.s == "/=" ? "#" : op.s == "=<" ? "<=" : op.s;
+      n->c = {lhs, rhs};
+      lhs = n;
+    }
+  }
+  NodeP unary() {
+    const Tok k = peek();
+    refuse_unsupported(k);
+    if (is_op("~")) { p++; NodeP n = mk(N_NOT, k); n->c = {expr(4)}; return n; }
+    if (is_op("-")) { p++; NodeP n = mk(N_NEG, k); n->c = {expr(12)}; return n; }
+    if (is_op("\\A") || is_op("\\E")) {
+      p++;
+      NodeP n = mk(N_QUANT, k);
+      n->s = k.s == "\\A" ? "A" : "E";
+      for (;;) {
+        if (peek().kind != TK_ID) fail(peek(), "expected a variable name");
+        n->vars.push_back(peek().s);
+        p++;
+        if (is_op(",")) { p++; continue; }
+        break;
+      }
+      if (!is_op("\\in")) fail(peek(), "expected \\in (an unbounded quantifier cannot be evaluated)");
+      p++;
+      NodeP set = expr(6);
+      expect(":");
+      n->c = {set, expr(1)};
+      return n;
+    }
+    if (is_id("DOMAIN")) { p++; NodeP n = mk(N_DOMAIN, k); n->c = {postfix()}; return n; }
+    return postfix();
+  }
+  NodeP postfix() {
+    NodeP n = primary();
+    for (;;) {
+      const Tok k = peek();
+      if (is_op("[")) {
+        p++;
+        NodeP ix = mk(N_INDEX, k);
+        ix->c = {n, expr(1)};
+        expect("]");
+        n = ix;
+      } else if (is_op(".")) {
+        p++;
+        if (peek().kind != TK_ID) fail(peek(), "expected a field name");
+        NodeP f = mk(N_FIELD, peek());
+        f->s = peek().s;
+        f->c = {n};
+        p++;
+        n = f;
+      } else if (is_op("'")) {
+        refuse_unsupported(k);
+      } else {
+        return n;
+      }
+    }
+  }
+  NodeP primary() {
+    const Tok k = peek();
+    refuse_unsupported(k);
+    if (k.kind == TK_NUM) { p++; NodeP n = mk(N_NUM, k); n->v = k.v; return n; }
+    if (k.kind == TK_ID) {
+      p++;
+      if (k.s == "TRUE" || k.s == "FALSE") { NodeP n = mk(N_BOOL, k); n->v = k.s == "TRUE"; return n; }
+      if (is_op("(")) {
+        if (k.s != "Cardinality" && k.s != "Len") fail(k, "unknown operator " + k.s + " (Cardinality and Len are the operators that take an argument)");
+        p++;
+        NodeP n = mk(N_CALL, k);
+        n->s = k.s;
+        n->c = {expr(1)};
+        expect(")");
+        return n;
+      }
+      NodeP n = mk(N_ID, k);
+      n->s = k.s;
+      return n;
+    }
+    if (is_op("(")) { p++; NodeP n = expr(1); expect(")"); n->paren = true; return n; }
+    if (is_op("[")) fail(k, "function and record constructors are not supported");
+    fail(k, k.kind == TK_EOF ? "expression expected before the end of the text" : "expression expected before '" + k.s + "'");
+  }
+};
+
+struct Binding { std::string name; int kind; int v; };       // kind 0: integer constant, 1: value constant (index + 1), 2: message loop v
+struct Def { NodeP body; };
+
+struct Compiler {
+  const Model& M;
+  bool symmetry;
+  const std::vector<std::string>& values;
+  WhereProgram& out;
+  std::vector<Binding> env;
+  std::map<std::string, Def> defs;
+  std::string compiling;                                      // the definition being compiled (recursion)
+  int cur = 0, msg_depth = 0;
+
+  Compiler(const Model& m, bool sym, const std::vector<std::string>& vals, WhereProgram& o) : M(m), symmetry(sym), values(vals), out(o) {}
+
+  void emit(int code, u32 arg, int delta) {
+    if (out.ops.size() + 1 >= (size_t)WHERE_MAX_OPS) throw Err{2, "state predicates: the program has more than " + std::to_string((int)WHERE_MAX_OPS) + " ops"};
+    out.ops.push_back(w_op(code, arg));
+    cur += delta;
+    if (cur > out.depth) out.depth = cur;
+    if (cur > (int)WHERE_MAX_DEPTH) throw Err{2, "state predicates: operand depth beyond " + std::to_string((int)WHERE_MAX_DEPTH)};
+  }
+  void push(int v) { emit(W_PUSH, (u32)v & 0xFFFFFFu, +1); }
+  void ldbits(int word, int shift, int width) { emit(W_LDBITS, (u32)word | ((u32)shift << 8) | ((u32)width << 14), +1); }
+  void ldm(int loop, int shift, int width) { emit(W_LDM, (u32)loop | ((u32)shift << 1) | ((u32)width << 7), +1); }
+  void bin(int code) { emit(code, 0, -1); }
+  int aword(int r) const { return 1 + (r - 1) * M.wpr; }
+
+  const Binding* lookup(const std::string& s) const {
+    for (size_t i = env.size(); i-- > 0;)
+      if (env[i].name == s) return &env[i];
+    return nullptr;
+  }
+  [[noreturn]] void fail(const NodeP& n, const std::string& why) const { fail_at(n->line, n->col, why); }
+  void want(const NodeP& n, int got, int need) const {
+    if (got != need) fail(n, std::string("type mismatch: ") + type_name(need) + " is needed here, this is " + type_name(got));
+  }
+  int value_literal(const std::string& s) const {
+    for (size_t v = 0; v < values.size(); v++)
+      if (values[v] == s) return (int)v + 1;
+    return 0;
+  }
+
+  // compile-time integers: literals, the model's constants, bound variables of unfolded quantifiers, + - \div of those
+  bool const_int(const NodeP& n, int* v) const {
+    switch (n->k) {
+      case N_NUM: *v = (int)n->v; return true;
+      case N_NEG: { int a; if (!const_int(n->c[0], &a)) return false; *v = -a; return true; }
+      case N_ID: {
+        if (const Binding* b = lookup(n->s)) { if (b->kind != 0) return false; *v = b->v; return true; }
+        if (n->s == "ReplicaCount") { *v = M.R; return true; }
+        if (n->s == "ClientCount") { *v = M.C; return true; }
+        if (n->s == "StartViewOnTimerLimit") { *v = M.L; return true; }
+        return false;
+      }
+      case N_CALL:
+        if (n->s == "Cardinality" && n->c[0]->k == N_ID && n->c[0]->s == "Values" && !lookup("Values")) { *v = M.n; return true; }
+        return false;
+      case N_BIN: {
+        int a, b;
+        if (n->s != "+" && n->s != "-" && n->s != "\\div") return false;
+        if (!const_int(n->c[0], &a) || !const_int(n->c[1], &b)) return false;
+        if (n->s == "+") *v = a + b;
+        else if (n->s == "-") *v = a - b;
+        else { *v = 0; if (b) { *v = a / b; if ((a % b) && ((a < 0) != (b < 0))) (*v)--; } }
+        return true;
+      }
+    }
+    return false;
+  }
+  bool const_value(const NodeP& n, int* v) const {
+    if (n->k != N_ID) return false;
+    if (const Binding* b = lookup(n->s)) { if (b->kind != 1) return false; *v = b->v; return true; }
+    if (!symmetry && value_literal(n->s)) { *v = value_literal(n->s); return true; }
+    return false;
+  }
+
+  // f[i1][i2]..: every index is a constant, or becomes a select chain over its candidates lo..hi.  `leaf` emits the load for one tuple of constants.
+  struct Ix { NodeP n; int lo, hi, type; };
+  void indexed(const std::vector<Ix>& ixs, size_t at, std::vector<int>& vals, int deflt, const std::function<void(const std::vector<int>&)>& leaf) {
+    if (at == ixs.size()) { leaf(vals); return; }
+    const Ix& x = ixs[at];
+    int v;
+    if (x.type == TY_INT ? const_int(x.n, &v) : const_value(x.n, &v)) {
+      if (v < x.lo || v > x.hi) { push(deflt); return; }
+      vals.push_back(v);
+      indexed(ixs, at + 1, vals, deflt, leaf);
+      vals.pop_back();
+      return;
+    }
+    push(deflt);
+    for (int k = x.lo; k <= x.hi; k++) {
+      want(x.n, compile(x.n), x.type);
+      push(k);
+      bin(W_EQ);
+      vals.push_back(k);
+      indexed(ixs, at + 1, vals, deflt, leaf);
+      vals.pop_back();
+      emit(W_SEL, 0, -2);
+    }
+  }
+
+  // n = root[..][..].field... : the accessors from the root outwards
+  struct Acc { bool field; std::string name; NodeP ix; NodeP at; };
+  NodeP flatten(NodeP n, std::vector<Acc>& acc) const {
+    while (n->k == N_INDEX || n->k == N_FIELD) {
+      acc.insert(acc.begin(), n->k == N_INDEX ? Acc{false, "", n->c[1], n} : Acc{true, n->s, nullptr, n});
+      n = n->c[0];
+    }
+    return n;
+  }
+  int entry_field(const NodeP& at, const std::string& f) {
+    const int k = f == "view_number" ? 0 : f == "operation" ? 1 : f == "client_id" ? 2 : f == "request_number" ? 3 : -1;
+    if (k < 0) fail(at, "a log entry has no field " + f + " (view_number, operation, client_id, request_number)");
+    emit(W_ENTF, (u32)k, 0);
+    return k == 1 ? TY_VALUE : TY_INT;
+  }
+  void emit_log_len(const NodeP& r) {                          // Len(rep_log[r])
+    std::vector<int> vals;
+    indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); emit(W_LOGLEN, 0, 0); });
+  }
+  // rep_log[r] as the argument of Len / DOMAIN: returns the index node r
+  NodeP log_of(const NodeP& n) const {
+    std::vector<Acc> acc;
+    NodeP root = flatten(n, acc);
+    if (root->k == N_ID && root->s == "rep_log" && !lookup("rep_log") && acc.size() == 1 && !acc[0].field) return acc[0].ix;
+    return nullptr;
+  }
+
+  int compile_path(const NodeP& n) {
+    std::vector<Acc> acc;
+    NodeP root = flatten(n, acc);
+    if (root->k != N_ID) fail(n, "only state variables and bound messages can be indexed or have fields");
+    const std::string& s = root->s;
+    auto shape = [&](std::initializer_list<bool> fields) {     // the accessors must be exactly: index (false) / field (true) in this order
+      if (acc.size() != fields.size()) return false;
+      size_t i = 0;
+      for (bool f : fields) if (acc[i++].field != f) return false;
+      return true;
+    };
+    std::vector<int> vals;
+    if (const Binding* b = lookup(s)) {
+      if (b->kind != 2) fail(n, s + " is not a message: it has no fields and cannot be indexed");
+      const int d = b->v;
+      if (!acc[0].field) fail(acc[0].at, "a message cannot be indexed");
+      const std::string& f = acc[0].name;
+      if (f == "message") {
+        emit(W_LDMENT, (u32)d, +1);
+        if (acc.size() == 1) return TY_ENTRY;
+        if (acc.size() == 2 && acc[1].field) return entry_field(acc[1].at, acc[1].name);
+        fail(n, "m.message is a log entry: one field at most");
+      }
+      if (acc.size() != 1) fail(n, "m." + f + " has no fields and cannot be indexed");
+      if (f == "type") { ldm(d, 0, 3); return TY_MTYPE; }
+      static const struct { const char* name; int shift, width; } F[] = {{"view_number", 3, 3}, {"dest", 6, 3}, {"source", 9, 3}, {"op_number", 12, 2},
+                                                                          {"commit_number", 14, 2}, {"last_normal_vn", 16, 3}, {"first_op", 19, 2}};
+      for (const auto& e : F)
+        if (f == e.name) { ldm(d, e.shift, e.width); return TY_INT; }
+      if (f == "log") fail(acc[0].at, "m.log is not supported");
+      fail(acc[0].at, "a message has no field " + f);
+    }
+    if (defs.count(s)) fail(n, s + " is a definition: it has no fields and cannot be indexed");
+    if (s == "messages") {
+      if (!shape({false})) fail(n, "messages[m] with m bound over DOMAIN messages is the supported form");
+      const Binding* b = acc[0].ix->k == N_ID ? lookup(acc[0].ix->s) : nullptr;
+      if (!b || b->kind != 2) fail(acc[0].ix, "messages[m]: m must be a variable bound over DOMAIN messages");
+      ldm(b->v, 21, 2);
+      return TY_INT;
+    }
+    static const struct { const char* name; int shift, width, type; } A[] = {
+        {"rep_status", 0, 2, TY_STATUS}, {"rep_view_number", 2, 3, TY_INT}, {"rep_op_number", 5, 2, TY_INT}, {"rep_commit_number", 7, 2, TY_INT},
+        {"rep_last_normal_view", 9, 3, TY_INT}, {"rep_sent_dvc", 12, 1, TY_BOOL}, {"rep_sent_sv", 13, 1, TY_BOOL}};
+    for (const auto& e : A)
+      if (s == e.name) {
+        if (!shape({false})) fail(n, s + "[r] is the supported form");
+        indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, e.type == TY_BOOL ? 0 : -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), e.shift, e.width); });
+        return e.type;
+      }
+    if (s == "rep_peer_op_number") {
+      if (!shape({false, false})) fail(n, "rep_peer_op_number[r][p] is the supported form");
+      indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, M.R, TY_INT}}, 0, vals, -1,
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 19 + 2 * (v[1] - 1), 2); });
+      return TY_INT;
+    }
+    if (s == "rep_client_table") {
+      if (!shape({false, false, true})) fail(n, "rep_client_table[r][c].request_number / .op_number / .executed are the supported forms");
+      const std::string& f = acc[2].name;
+      const int off = f == "request_number" ? 0 : f == "op_number" ? 2 : f == "executed" ? 4 : -1;
+      if (off < 0) fail(acc[2].at, "a client-table row has no field " + f);
+      indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, M.C, TY_INT}}, 0, vals, off == 4 ? 0 : -1,
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 29 + 5 * (v[1] - 1) + off, off == 4 ? 1 : 2); });
+      return off == 4 ? TY_BOOL : TY_INT;
+    }
+    if (s == "rep_log") {
+      if (!shape({false, false}) && !shape({false, false, true})) fail(n, "rep_log[r][i], its fields, Len(rep_log[r]) and DOMAIN rep_log[r] are the supported forms");
+      indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, 3, TY_INT}}, 0, vals, 0,      // outside the log: the absent entry
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 8 * (v[1] - 1), 8); });
+      return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
+    }
+    if (s == "aux_client_acked") {
+      if (!shape({false})) fail(n, "aux_client_acked[v] is the supported form");
+      indexed({Ix{acc[0].ix, 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(2); bin(W_EQ); });
+      return TY_BOOL;
+    }
+    if (s == "rep_svc_recv" || s == "rep_dvc_recv") fail(n, s + ": only Cardinality(" + s + "[r]) is supported");
+    compile(root);                                            // unknown identifier / not indexable: the error names it
+    fail(n, s + " has no fields and cannot be indexed");
+  }
+
+  // the members lo..hi of a constant set; false = not such a set
+  bool const_set(const NodeP& s, int* lo, int* hi, int* kind) {
+    *kind = 0;
+    if (s->k == N_ID && !lookup(s->s) && !defs.count(s->s)) {
+      if (s->s == "replicas") { *lo = 1; *hi = M.R; return true; }
+      if (s->s == "clients") { *lo = 1; *hi = M.C; return true; }
+      if (s->s == "Values") { *lo = 1; *hi = M.n; *kind = 1; return true; }
+    }
+    if (s->k == N_BIN && s->s == "..") {
+      if (!const_int(s->c[0], lo) || !const_int(s->c[1], hi)) fail(s, "the bounds of a range must be constants");
+      if (*hi - *lo > 64) fail(s, "range too large to unfold");
+      return true;
+    }
+    return false;
+  }
+
+  int compile_quant(const NodeP& n, size_t var) {
+    const NodeP& set = n->c[0];
+    const bool forall = n->s == "A";
+    if (var == n->vars.size()) { want(n->c[1], compile(n->c[1]), TY_BOOL); out.n_bodies++; return TY_BOOL; }
+    const std::string& name = n->vars[var];
+    int lo, hi, kind;
+    NodeP logr;
+    if (const_set(set, &lo, &hi, &kind)) {
+      if (lo > hi) { push(forall); return TY_BOOL; }
+      for (int k = lo; k <= hi; k++) {
+        env.push_back(Binding{name, kind, k});
+        compile_quant(n, var + 1);
+        env.pop_back();
+        if (k > lo) bin(forall ? W_AND : W_OR);
+      }
+      return TY_BOOL;
+    }
+    if (set->k == N_DOMAIN && (logr = log_of(set->c[0]))) {    // 1..Len(rep_log[r]): unfolded over the three positions, each guarded by its presence
+      for (int k = 1; k <= 3; k++) {
+        push(k);
+        emit_log_len(logr);
+        bin(W_LE);
+        env.push_back(Binding{name, 0, k});
+        compile_quant(n, var + 1);
+        env.pop_back();
+        bin(forall ? W_IMP : W_AND);
+        if (k > 1) bin(forall ? W_AND : W_OR);
+      }
+      return TY_BOOL;
+    }
+    if (set->k == N_DOMAIN && set->c[0]->k == N_ID && set->c[0]->s == "messages" && !lookup("messages")) {
+      if (msg_depth >= 2) fail(n, "at most two nested quantifiers over DOMAIN messages");
+      const int d = msg_depth++;
+      if (msg_depth > out.msg_loops) out.msg_loops = msg_depth;
+      const size_t begin = out.ops.size();
+      emit(W_MBEGIN, 0, 0);
+      env.push_back(Binding{name, 2, d});
+      compile_quant(n, var + 1);
+      env.pop_back();
+      out.ops[begin] = w_op(W_MBEGIN, (u32)out.ops.size() | ((u32)d << 12) | ((u32)forall << 13));
+      emit(W_MEND, (u32)d | ((u32)forall << 1) | ((u32)(begin + 1) << 2), 0);
+      msg_depth--;
+      return TY_BOOL;
+    }
+    fail(set, "a quantifier ranges over replicas, clients, Values, a..b, DOMAIN rep_log[r] or DOMAIN messages");
+  }
+
+  int compile(const NodeP& n) {
+    switch (n->k) {
+      case N_NUM: push((int)n->v); return TY_INT;
+      case N_BOOL: push((int)n->v); return TY_BOOL;
+      case N_NOT: want(n->c[0], compile(n->c[0]), TY_BOOL); emit(W_NOT, 0, 0); return TY_BOOL;
+      case N_NEG: push(0); want(n->c[0], compile(n->c[0]), TY_INT); bin(W_SUB); return TY_INT;
+      case N_QUANT: return compile_quant(n, 0);
+      case N_INDEX:
+      case N_FIELD: return compile_path(n);
+      case N_DOMAIN: fail(n, "DOMAIN is supported after \\in only (DOMAIN rep_log[r], DOMAIN messages, DOMAIN aux_client_acked)");
+      case N_CALL: {
+        const NodeP& a = n->c[0];
+        int v;
+        if (const_int(n, &v)) { push(v); return TY_INT; }
+        if (n->s == "Len") {
+          NodeP r = log_of(a);
+          if (!r) fail(n, "Len(rep_log[r]) is the supported form");
+          emit_log_len(r);
+          return TY_INT;
+        }
+        std::vector<Acc> acc;
+        NodeP root = flatten(a, acc);
+        if (root->k == N_ID && !lookup(root->s) && acc.size() == 1 && !acc[0].field && (root->s == "rep_svc_recv" || root->s == "rep_dvc_recv")) {
+          const bool svc = root->s == "rep_svc_recv";
+          std::vector<int> vals;
+          indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& r) {
+            if (svc) { ldbits(aword(r[0]), 14, M.R); emit(W_POPC, 0, 0); return; }
+            for (int s = 1; s <= M.R; s++) {                   // x-slot s of the block: bit 0 = a DoViewChange from s is held
+              ldbits(aword(r[0]) + 1 + (s >> 1), 32 * (s & 1), 1);
+              if (s > 1) bin(W_ADD);
+            }
+          });
+          return TY_INT;
+        }
+        fail(n, "Cardinality(Values), Cardinality(rep_svc_recv[r]) and Cardinality(rep_dvc_recv[r]) are the supported forms");
+      }
+      case N_ID: {
+        const std::string& s = n->s;
+        if (const Binding* b = lookup(s)) {
+          if (b->kind == 2) fail(n, "a message is used through its fields (" + s + ".type, messages[" + s + "], ...)");
+          push(b->v);
+          return b->kind == 1 ? TY_VALUE : TY_INT;
+        }
+        auto d = defs.find(s);
+        if (d != defs.end()) {                                  // an earlier definition, inlined (nullary: it sees no bound variable)
+          std::vector<Binding> saved;
+          saved.swap(env);
+          const int md = msg_depth;
+          const int t = compile(d->second.body);
+          msg_depth = md;
+          env.swap(saved);
+          return t;
+        }
+        if (s == compiling) fail(n, s + " refers to itself");
+        int v;
+        if (const_int(n, &v)) { push(v); return TY_INT; }
+        static const struct { const char* name; int code, type; } K[] = {
+            {"Normal", ST_NORMAL, TY_STATUS}, {"ViewChange", ST_VIEWCHANGE, TY_STATUS}, {"Recovering", ST_RECOVERING, TY_STATUS},
+            {"StartViewChangeMsg", T_SVC, TY_MTYPE}, {"PrepareMsg", T_PREPARE, TY_MTYPE}, {"PrepareOkMsg", T_PREPAREOK, TY_MTYPE},
+            {"DoViewChangeMsg", T_DVC, TY_MTYPE}, {"StartViewMsg", T_SV, TY_MTYPE}, {"GetStateMsg", T_GETSTATE, TY_MTYPE},
+            {"NewStateMsg", T_NEWSTATE, TY_MTYPE}, {"Nil", 0, TY_VALUE}};
+        for (const auto& e : K)
+          if (s == e.name) { push(e.code); return e.type; }
+        if (value_literal(s)) {
+          if (symmetry) fail(n, "the model value " + s + " cannot be named under SYMMETRY: bind a variable over Values instead");
+          push(value_literal(s));
+          return TY_VALUE;
+        }
+        if (s == "aux_svc") { ldbits(0, 8, 3); return TY_INT; }
+        static const char* const STATE[] = {"rep_status", "rep_view_number", "rep_op_number", "rep_commit_number", "rep_last_normal_view", "rep_sent_dvc", "rep_sent_sv",
+                                            "rep_peer_op_number", "rep_client_table", "rep_log", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};
+        for (const char* e : STATE)
+          if (s == e) fail(n, s + " is a function: apply it to an index");
+        if (s == "replicas" || s == "clients" || s == "Values") fail(n, s + " is a set: it can be quantified over or tested with \\in");
+        static const char* const UNLOWERED[] = {"aux_restart", "rep_rec_number", "rep_rec_recv", "RecoveryMsg", "RecoveryResponseMsg"};
+        for (const char* e : UNLOWERED)
+          if (s == e) fail(n, s + " belongs to the recovery protocol, which is not lowered");
+        fail(n, "unknown identifier " + s + " (a definition must precede its use; a variable must be bound by \\A or \\E)");
+      }
+      case N_BIN: {
+        const std::string& o = n->s;
+        if (o == "/\\" || o == "\\/" || o == "=>" || o == "<=>") {
+          want(n->c[0], compile(n->c[0]), TY_BOOL);
+          want(n->c[1], compile(n->c[1]), TY_BOOL);
+          bin(o == "/\\" ? W_AND : o == "\\/" ? W_OR : o == "=>" ? W_IMP : W_EQ);
+          return TY_BOOL;
+        }
+        if (o == "+" || o == "-" || o == "\\div") {
+          int v;
+          if (const_int(n, &v)) { push(v); return TY_INT; }
+          want(n->c[0], compile(n->c[0]), TY_INT);
+          want(n->c[1], compile(n->c[1]), TY_INT);
+          bin(o == "+" ? W_ADD : o == "-" ? W_SUB : W_DIV);
+          return TY_INT;
+        }
+        if (o == "=" || o == "#") {
+          const int a = compile(n->c[0]), b = compile(n->c[1]);
+          if (a != b) fail(n, std::string("type mismatch: ") + type_name(a) + " is compared with " + type_name(b));
+          bin(o == "=" ? W_EQ : W_NE);
+          return TY_BOOL;
+        }
+        if (o == "<" || o == "<=" || o == ">" || o == ">=") {
+          want(n->c[0], compile(n->c[0]), TY_INT);
+          want(n->c[1], compile(n->c[1]), TY_INT);
+          bin(o == "<" ? W_LT : o == "<=" ? W_LE : o == ">" ? W_GT : W_GE);
+          return TY_BOOL;
+        }
+        if (o == "\\in") {
+          const NodeP& set = n->c[1];
+          int lo, hi, kind;
+          NodeP logr;
+          if (set->k == N_DOMAIN && set->c[0]->k == N_ID && set->c[0]->s == "aux_client_acked" && !lookup("aux_client_acked")) {
+            std::vector<int> vals;
+            indexed({Ix{n->c[0], 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(0); bin(W_NE); });
+            return TY_BOOL;
+          }
+          if (const_set(set, &lo, &hi, &kind)) {
+            want(n->c[0], compile(n->c[0]), kind ? TY_VALUE : TY_INT);
+            push(lo); bin(W_GE);
+            compile(n->c[0]);
+            push(hi); bin(W_LE);
+            bin(W_AND);
+            return TY_BOOL;
+          }
+          if (set->k == N_DOMAIN && (logr = log_of(set->c[0]))) {
+            want(n->c[0], compile(n->c[0]), TY_INT);
+            push(1); bin(W_GE);
+            compile(n->c[0]);
+            emit_log_len(logr);
+            bin(W_LE);
+            bin(W_AND);
+            return TY_BOOL;
+          }
+          fail(set, "\\in is supported for replicas, clients, Values, a..b, DOMAIN rep_log[r] and DOMAIN aux_client_acked");
+        }
+        if (o == "..") fail(n, "a range can be quantified over or tested with \\in");
+        fail(n, "operator " + o + " is not supported");
+      }
+    }
+    fail(n, "unsupported expression");
+  }
+};
+
+}  // namespace where_detail
+
+// 0 = compiled; 1 = refused (VSRMC_E_ARG), 2 = beyond a cap (VSRMC_E_REP): *err says why
+inline int where_compile(const Model& M, bool symmetry, const std::vector<std::string>& value_names, const std::string& text, WhereProgram* out, std::string* err) {
+  using namespace where_detail;
+  *out = WhereProgram();
+  try {
+    Parser P;
+    P.t = lex(text);
+    Compiler C(M, symmetry, value_names, *out);
+    bool has_defs = false;
+    for (const Tok& k : P.t) has_defs = has_defs || (k.kind == TK_OP && k.s == "==");
+    auto export_top = [&](const std::string& name, const Tok& at) {
+      if (out->names.size() >= (size_t)WHERE_MAX_EXPORTS) fail_at(at.line, at.col, "more than 8 exported definitions (write LOCAL Name == ... for a helper)");
+      C.emit(W_OUT, (u32)out->names.size(), -1);
+      out->names.push_back(name);
+    };
+    if (!has_defs) {
+      const Tok first = P.peek();
+      NodeP e = P.expr(1);
+      if (P.peek().kind != TK_EOF) P.fail(P.peek(), "unexpected '" + P.peek().s + "' after the expression");
+      C.want(e, C.compile(e), TY_BOOL);
+      export_top("where", first);
+    } else {
+      while (P.peek().kind != TK_EOF) {
+        bool local = false;
+        if (P.is_id("LOCAL")) { local = true; P.p++; }
+        const Tok name = P.peek();
+        if (name.kind != TK_ID || !P.is_op("==", 1)) P.fail(name, "expected a definition: Name == expression");
+        if (C.defs.count(name.s)) P.fail(name, name.s + " is defined twice");
+        P.p += 2;
+        NodeP e = P.expr(1);
+        if (local) {                                            // type-checked where it is used; checked here too, its code discarded
+          WhereProgram scratch;
+          Compiler T(M, symmetry, value_names, scratch);
+          T.defs = C.defs;
+          T.compiling = name.s;
+          T.compile(e);
+        } else {
+          C.compiling = name.s;
+          C.want(e, C.compile(e), TY_BOOL);
+          C.compiling.clear();
+          export_top(name.s, name);
+        }
+        C.defs[name.s] = Def{e};
+      }
+      if (out->names.empty()) fail_at(1, 1, "no exported definition");
+    }
+    C.emit(W_END, 0, 0);
+  } catch (const Err& e) {
+    *err = e.msg;
+    *out = WhereProgram();
+    return e.code;
+  }
+  return 0;
+}
+
+}  // namespace vsr

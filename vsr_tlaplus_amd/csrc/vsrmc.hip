@@ -23,6 +23,8 @@
 #include "vsr_kernels.hpp"
 #include "vsr_probe_scan.hpp"
 #include "vsr_terminal.hpp"
+#include "vsr_where.hpp"
+#include "vsr_where_parse.hpp"
 
 #define VSRMC_FP_VERSION 2          // fingerprint function of this build; checkpoints of another version are refused
 
@@ -114,4 +116,5 @@ extern "C" {
 #include "vsr_shard_loop.hpp"    // the sharded level loop in C++ over RCCL / host callbacks
 #include "host_tlcfp.hpp"        // TLC's FP64 as a mode
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
+#include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

@@ -5,7 +5,8 @@
 // `-deadlock` (= do NOT check deadlock) is the default here because the spec has terminal states; pass
 // -checkDeadlock to stop at the first state without successors like stock TLC would: the newest level is scanned for terminal states before it is
 // expanded (vsrmc_checker_terminal_scan) and the behaviour into the one with the smallest fingerprint is printed.  -terminalReport scans every
-// stored level without stopping.
+// stored level without stopping.  -predicates FILE with -reach / -invariant / -whereReport evaluates the user's own state predicates (k_where) on every
+// stored level, where -checkDeadlock scans.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +33,14 @@ static void usage() {
       "  -terminalReport   scan every stored level for terminal states without stopping; one summary line at the end.  A terminal state in\n"
       "                    which AllReplicasMoveToSameView is false is printed with its behaviour (last line: Stuttering): a counter-example\n"
       "                    to ViewChangeCompletes.  Finding none is no verdict: behaviours that loop are not examined\n"
+      "  -predicates FILE  state predicates in TLA+ syntax (VSR.tla only; the language: csrc/vsr_where_parse.hpp, an example: tools/predicates_example.txt):\n"
+      "                    one expression, or definitions Name == expr (at most 8 that are not LOCAL).  Used by:\n"
+      "  -reach NAME[,NAME]      every stored level is scanned before it is expanded; the first level with a state that satisfies NAME ends the run:\n"
+      "                    \"State satisfying NAME found at depth d\" and the behaviour into the one with the smallest fingerprint (a shortest one;\n"
+      "                    -dumpTrace tla FILE writes it).  Exit 0 when found, 14 when the search ended without one\n"
+      "  -invariant NAME[,NAME]  the same scan for ~NAME: a state in which NAME is false is reported like a violation of a built-in invariant (exit 12)\n"
+      "  -whereReport      count the states that satisfy each exported predicate, level by level, without stopping; with -json a \"where\" object in\n"
+      "                    the level lines.  Levels that are never stored (the Virtual / Probe lines) are not examined, and the report says how many\n"
       "  -maxDepth N       stop after N BFS levels (Init = level 1)\n"
       "  -device D         HIP device ordinal (default 0)\n"
       "  -gpus N           N > 1: run the sharded checker on N GPUs of this node (re-executes as\n"
@@ -120,7 +129,8 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 int main(int argc, char** argv) {
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) return exec_sharded(argc, argv, i);
-  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file;
+  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg;
+  bool where_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
   bool check_deadlock = false, no_tla = false, json = false, simulate = false, host_frontier = false, probe_last = false, coverage = false, audit = false, terminal_report = false;
@@ -164,6 +174,10 @@ int main(int argc, char** argv) {
     else if (a == "-coverage") coverage = true;
     else if (a == "-audit") audit = true;
     else if (a == "-terminalReport") terminal_report = true;
+    else if (a == "-predicates" && i + 1 < argc) predicates_file = argv[++i];
+    else if (a == "-reach" && i + 1 < argc) reach_arg = argv[++i];
+    else if (a == "-invariant" && i + 1 < argc) invariant_arg = argv[++i];
+    else if (a == "-whereReport") where_report = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -256,6 +270,54 @@ int main(int argc, char** argv) {
                 r.seconds, r.seconds > 0 ? (double)r.steps / r.seconds : 0.0);
     vsrmc_model_destroy(m);
     return code;
+  }
+  // state predicates (-predicates FILE): `w_all` = the file as written (-whereReport counts its exported names); `w_query` = the names of -reach, then
+  // the negations of the names of -invariant, over the file with every definition made LOCAL
+  vsrmc_where *w_all = nullptr, *w_query = nullptr;
+  std::vector<std::string> where_names, query_names;
+  size_t n_reach = 0;
+  if (!reach_arg.empty() || !invariant_arg.empty() || where_report) {
+    if (predicates_file.empty()) { std::fprintf(stderr, "Error: -reach / -invariant / -whereReport need -predicates FILE\n"); return 2; }
+    std::ifstream pf(predicates_file, std::ios::binary);
+    if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", predicates_file.c_str()); return 1; }
+    std::stringstream pss;
+    pss << pf.rdbuf();
+    const std::string text = pss.str();
+    if (vsrmc_where_compile(m, text.c_str(), &w_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", predicates_file.c_str(), vsrmc_last_error()); return 1; }
+    vsrmc_where_desc wd;
+    vsrmc_where_describe(w_all, &wd);
+    for (int k = 0; k < wd.n_names; k++) where_names.push_back(wd.names[k]);
+    auto split = [&](const std::string& arg) {
+      std::stringstream ss(arg);
+      std::string name;
+      while (std::getline(ss, name, ','))
+        if (!name.empty()) query_names.push_back(name);
+    };
+    split(reach_arg);
+    n_reach = query_names.size();
+    split(invariant_arg);
+    if (!query_names.empty()) {
+      std::string local;                                          // every `Name ==` that is not LOCAL already gets the word in front
+      for (size_t i = 0; i < text.size(); i++) {
+        if (text.compare(i, 2, "==") == 0 && (i == 0 || text[i - 1] != '=') && (i + 2 >= text.size() || text[i + 2] != '=')) {
+          size_t e = local.size();
+          while (e > 0 && std::isspace((unsigned char)local[e - 1])) e--;
+          size_t b = e;
+          while (b > 0 && (std::isalnum((unsigned char)local[b - 1]) || local[b - 1] == '_')) b--;
+          size_t q = b;
+          while (q > 0 && std::isspace((unsigned char)local[q - 1])) q--;
+          if (b < e && !(q >= 5 && local.compare(q - 5, 5, "LOCAL") == 0)) local.insert(b, "LOCAL ");
+        }
+        local.push_back(text[i]);
+      }
+      for (size_t k = 0; k < query_names.size(); k++) {
+        bool known = false;
+        for (const std::string& n : where_names) known = known || n == query_names[k];
+        if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", predicates_file.c_str(), query_names[k].c_str()); return 2; }
+        local += "\nQuery" + std::to_string(k) + " == " + (k < n_reach ? "" : "~") + query_names[k];
+      }
+      if (vsrmc_where_compile(m, local.c_str(), &w_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+    }
   }
   vsrmc_options o;
   vsrmc_options_default(&o);
@@ -358,7 +420,40 @@ int main(int argc, char** argv) {
     if (ti.n_unsettled && !uns_level) { uns_level = ti.level; uns_fp = ti.min_fp_unsettled; }
     return 0;
   };
+  // state predicates: the newest stored level is scanned where the terminal scan scans it
+  struct WhereRow { int level; unsigned long long n_states; unsigned long long count[8]; };
+  std::vector<WhereRow> where_rows;
+  vsrmc_where_info wi_all, wi_query;
+  std::memset(&wi_all, 0, sizeof(wi_all));
+  std::memset(&wi_query, 0, sizeof(wi_query));
+  int where_last = 0, where_hit = -1;
+  unsigned long long where_unexamined = 0;
+  bool where_scanned_this_step = false;
+  auto where_newest = [&]() -> int {
+    where_scanned_this_step = false;
+    vsrmc_level_info st;
+    if (vsrmc_checker_status(c, &st) != 0) return -1;
+    if (st.reserved0 != 0 || st.level == where_last || st.n_new == 0) return 0;
+    int32_t r = 0;
+    if (w_all && where_report && (r = vsrmc_checker_where_scan(c, w_all, &wi_all)) != 0) return r == VSRMC_E_STATE ? 0 : r;
+    if (w_query && (r = vsrmc_checker_where_scan(c, w_query, &wi_query)) != 0) return r == VSRMC_E_STATE ? 0 : r;
+    where_last = st.level;
+    where_scanned_this_step = true;
+    if (where_report) {
+      WhereRow row{wi_all.level, (unsigned long long)wi_all.n_states, {0}};
+      for (size_t k = 0; k < where_names.size(); k++) row.count[k] = (unsigned long long)wi_all.count[k];
+      where_rows.push_back(row);
+    }
+    if (w_query) {                                                // an invariant's violation is reported before a reachability hit of the same level
+      for (size_t k = n_reach; k < query_names.size() && where_hit < 0; k++)
+        if (wi_query.count[k]) where_hit = (int)k;
+      for (size_t k = 0; k < n_reach && where_hit < 0; k++)
+        if (wi_query.count[k]) where_hit = (int)k;
+    }
+    return 0;
+  };
   // Init .. the level-`level` state `fp`, printed the way a violation is; `stutter`: a last line "State k+1: Stuttering"
+  const char* behaviour_header = "Error: The behavior up to this point is:";
   auto print_behaviour_to = [&](int level, uint64_t fp, bool stutter) -> bool {
     uint64_t cap_w = ((uint64_t)level + 2) * (uint64_t)lay.max_record_words, n_states = 0;
     std::vector<uint64_t> words(cap_w), off((size_t)level + 2);
@@ -367,7 +462,7 @@ int main(int argc, char** argv) {
       std::printf("Error: %s\n", vsrmc_last_error());
       return false;
     }
-    std::printf("Error: The behavior up to this point is:\n");
+    std::printf("%s\n", behaviour_header);
     for (uint64_t t = 0; t < n_states; t++) {
       int64_t need = 0;
       vsrmc_model_format_state(m, &words[off[t]], nullptr, 0, &need);
@@ -428,6 +523,11 @@ int main(int argc, char** argv) {
       if (rc != 0) break;
       if (check_deadlock && scanned_this_step && ti.n_terminal) { deadlocked = true; break; }
     }
+    if (w_all) {
+      rc = where_newest();
+      if (rc != 0) break;
+      if (where_hit >= 0) break;
+    }
     rc = vsrmc_checker_advance(c, &info, &probed, &what);
     if (rc != 0) break;
     if (what == 3) {                                              // no new level: the deep search was re-based (the levels shrink again)
@@ -443,6 +543,7 @@ int main(int argc, char** argv) {
       depth = info.level;
       rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
       if (terminal_report && !scanned_this_step) { unlisted_levels++; unlisted_deadlocks += (unsigned long long)info.deadlocks; }   // the level this pass expanded has no records
+      if (w_all) where_unexamined++;                              // the level this pass inserted is never stored
       if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -474,10 +575,21 @@ int main(int argc, char** argv) {
     if (info.n_new) depth = info.level;
     if (info.n_new) rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::string where_json;                                       // (of the level this step expanded, like terminal / unsettled)
+    if (json && where_report && where_scanned_this_step) {
+      where_json = ", \"where\": {";
+      for (size_t k = 0; k < where_names.size(); k++)
+        where_json += (k ? ", \"" : "\"") + where_names[k] + "\": " + std::to_string((unsigned long long)wi_all.count[k]);
+      where_json += "}";
+    }
     if (json && scanned_this_step)                                // (terminal / unsettled: of the level this step expanded, like deadlocks)
-      std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu, \"seconds\": %.4f}\n",
+      std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu%s, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
-                  (unsigned long long)info.deadlocks, (unsigned long long)ti.n_terminal, (unsigned long long)ti.n_unsettled, dt);
+                  (unsigned long long)info.deadlocks, (unsigned long long)ti.n_terminal, (unsigned long long)ti.n_unsettled, where_json.c_str(), dt);
+    else if (json && !where_json.empty())
+      std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu%s, \"seconds\": %.4f}\n",
+                  info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
+                  (unsigned long long)info.deadlocks, where_json.c_str(), dt);
     else if (json)
       std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -494,6 +606,14 @@ int main(int argc, char** argv) {
   // the report covers the newest stored level too when the loop ended before expanding it (-maxDepth, a violation, a full seen-set); an exhausted search's
   // last level is empty and a level already scanned is not scanned again (scan_newest)
   if (terminal_report && rc == 0 && !deadlocked) rc = scan_newest();
+  if (w_all && rc == 0 && where_hit < 0 && !deadlocked) {
+    rc = where_newest();
+    if (json && where_report && where_scanned_this_step && rc == 0) {   // the newest level was not expanded: a line of its own
+      std::printf("{\"level\": %d, \"expanded\": false, \"where\": {", wi_all.level);
+      for (size_t k = 0; k < where_names.size(); k++) std::printf("%s\"%s\": %llu", k ? ", " : "", where_names[k].c_str(), (unsigned long long)wi_all.count[k]);
+      std::printf("}}\n");
+    }
+  }
   double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   int exit_code = 0;
   if (rc != 0) {
@@ -528,6 +648,14 @@ int main(int argc, char** argv) {
       }
       exit_code = 12;   // TLC's exit code for a safety violation
     }
+  } else if (where_hit >= (int)n_reach) {                       // a user's invariant: reported like a built-in one
+    std::printf("Error: Invariant %s is violated.\n", query_names[where_hit].c_str());
+    exit_code = print_behaviour_to(wi_query.level, wi_query.min_fp[where_hit], false) ? 12 : 1;
+  } else if (where_hit >= 0) {
+    std::printf("State satisfying %s found at depth %d (%llu of the level's %llu states satisfy it).\n", query_names[where_hit].c_str(), wi_query.level,
+                (unsigned long long)wi_query.count[where_hit], (unsigned long long)wi_query.n_states);
+    behaviour_header = "The behavior up to this point is:";
+    exit_code = print_behaviour_to(wi_query.level, wi_query.min_fp[where_hit], false) ? 0 : 1;
   } else if (deadlocked && scanned_this_step && ti.n_terminal) {  // found by the scan, before the level was expanded: there is a behaviour to show
     std::printf("Error: Deadlock reached (%llu state(s) of level %d have no successor).\n", (unsigned long long)ti.n_terminal, ti.level);
     exit_code = print_behaviour_to(ti.level, ti.min_fp, false) ? 11 : 1;
@@ -564,6 +692,28 @@ int main(int argc, char** argv) {
       std::printf("No terminal state with AllReplicasMoveToSameView false was found: this is no verdict on ViewChangeCompletes (a behaviour that never reaches a "
                   "terminal state could still violate it; loops are not examined).\n");
     }
+  }
+  if (n_reach && rc == 0 && where_hit < 0 && !violated && !probed_violation && !deadlocked) {
+    for (size_t k = 0; k < n_reach; k++)
+      std::printf("No state satisfying %s was found in the %s.\n", query_names[k].c_str(),
+                  where_unexamined ? "levels that were examined" : info.n_new == 0 && !incomplete ? "state space" : "levels searched");
+    if (where_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.\n", where_unexamined);
+    exit_code = exit_code ? exit_code : 14;
+  }
+  if (where_report && rc == 0) {
+    for (size_t k = 0; k < where_names.size(); k++) {
+      unsigned long long total = 0, states = 0;
+      size_t with = 0;
+      for (const WhereRow& r : where_rows) { total += r.count[k]; with += r.count[k] ? 1 : 0; }
+      for (const WhereRow& r : where_rows) states += r.n_states;
+      std::printf("Where report: %s holds in %llu of %llu states, in %zu of %zu examined levels", where_names[k].c_str(), total, states, with, where_rows.size());
+      bool first = true;
+      for (const WhereRow& r : where_rows)
+        if (r.count[k]) { std::printf("%slevel %d: %llu", first ? " (" : ", ", r.level, r.count[k]); first = false; }
+      std::printf("%s.\n", first ? "" : ")");
+    }
+    if (where_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.  Probed levels are not examined either.\n", where_unexamined);
+    if (probe2_at > 0 || probe3_at > 0) std::printf("The levels of -probe2At / -probe3At were not examined: they have no records.\n");
   }
   if (coverage) {   // ≙ tlc2.TLC -coverage, per action of Next: successors generated in the stored levels (probed / virtual levels not included)
     std::printf("The coverage statistics (successors generated per action):\n");
@@ -617,6 +767,8 @@ int main(int argc, char** argv) {
     }
   }
   if (c) vsrmc_checker_destroy(c);
+  if (w_all) vsrmc_where_destroy(w_all);
+  if (w_query) vsrmc_where_destroy(w_query);
   vsrmc_model_destroy(m);
   return exit_code;
 }
