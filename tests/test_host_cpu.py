@@ -268,3 +268,11 @@ def test_test_hooks_live_in_the_hooks_library_only(vt):
         assert hasattr(lib, name), name
         assert not hasattr(plib, name) and name.encode() not in prod, name
     assert b"vsrmc_test_" not in prod
+    # the seen-set / winner-set / partition hooks (csrc/host_test_table.hpp, tests/seen_set_worker.py) and their two hook-only kernels: hooks library only
+    table_hooks = [n for n in capi.HOOK_SYMBOLS if n.startswith(("vsrmc_test_table_", "vsrmc_test_wset_"))]
+    assert len(table_hooks) == 18 and "vsrmc_test_table_claim" in table_hooks and "vsrmc_test_wset_take" in table_hooks
+    for name in table_hooks:
+        assert hasattr(lib, name) and name.encode() in hooks, name
+        assert not hasattr(plib, name), name
+    for needle in (b"vsrmc_test_table_", b"vsrmc_test_wset_", b"k_test_wset_take", b"k_test_probe_lookup"):
+        assert needle not in prod and needle in hooks, needle

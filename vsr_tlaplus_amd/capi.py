@@ -194,6 +194,25 @@ SYMBOLS = {
 # test hooks: exported by libvsrmc_hooks.so only (-DVSRMC_TEST_HOOKS; VSRMC_LIB points a test's child process at it), declared when present
 HOOK_SYMBOLS = {
     "vsrmc_test_checker_seed_records": (C.c_int32, [V, V, V, C.c_uint64]),
+    # csrc/host_test_table.hpp: the seen-set kernels of a checker, k_partition and a stand-alone winner set, one launch at a time (tests/seen_set_worker.py)
+    "vsrmc_test_table_clear": (C.c_int32, [V]),
+    "vsrmc_test_table_claim": (C.c_int32, [V, V, C.c_uint64, C.c_int32, C.c_int32, V, V]),
+    "vsrmc_test_table_dump": (C.c_int32, [V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_test_table_grow": (C.c_int32, [V]),
+    "vsrmc_test_table_untake": (C.c_int32, [V, C.c_int32]),
+    "vsrmc_test_table_level_checksum": (C.c_int32, [V, C.c_int32, V]),
+    "vsrmc_test_table_lookup": (C.c_int32, [V, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vsrmc_test_table_walk": (C.c_int32, [V, C.c_uint64, C.c_int32, V, V, C.POINTER(C.c_int32)]),
+    "vsrmc_test_table_probe_lookup": (C.c_int32, [V, V, C.c_uint64, V, V]),
+    "vsrmc_test_table_export_import": (C.c_int32, [V, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
+    "vsrmc_test_table_partition": (C.c_int32, [C.c_int32, V, V, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "vsrmc_test_wset_create": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(V)]),
+    "vsrmc_test_wset_destroy": (None, [V]),
+    "vsrmc_test_wset_dump": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_test_wset_grow": (C.c_int32, [V]),
+    "vsrmc_test_wset_export_import": (C.c_int32, [V, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
+    "vsrmc_test_wset_insert": (C.c_int32, [V, C.c_int32, C.c_int32, V, V, V, C.c_uint64, C.c_int32, V, V, C.c_uint64, V, C.c_uint64, V]),
+    "vsrmc_test_wset_take": (C.c_int32, [V, V, C.c_uint64, C.c_int32, C.c_uint32, V]),
 }
 
 _lib = None

@@ -113,6 +113,7 @@ extern "C" {
 #include "host_shard.hpp"        // phases of a sharded level (C ABI)
 #include "host_checkpoint.hpp"   // checkpoint / recover, accessors, traces, destroy
 #include "host_test_seed.hpp"    // TEST HOOK (-DVSRMC_TEST_HOOKS only): a search seeded with a caller's records
+#include "host_test_table.hpp"   // TEST HOOKS (-DVSRMC_TEST_HOOKS only): the seen-set kernels, the winner set and k_partition one launch at a time
 #include "vsr_shard_loop.hpp"    // the sharded level loop in C++ over RCCL / host callbacks
 #include "host_tlcfp.hpp"        // TLC's FP64 as a mode
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
