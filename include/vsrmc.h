@@ -310,7 +310,7 @@ typedef struct vsrmc_where_desc {
   int32_t n_ops, depth;                            /* program length (the final END included), operand-stack depth */
   int32_t msg_loops;                               /* nesting of the quantifiers over DOMAIN messages that remain as loops: 0, 1 or 2 */
   int32_t n_bodies;                                /* quantifier bodies after unfolding (\E r1, r2 \in replicas at ReplicaCount 3: 9) */
-  int32_t reserved0;
+  int32_t step;                                    /* 1: a step program (vsrmc_step_compile, below); 0: a state program */
   char names[8][64];
 } vsrmc_where_desc;
 typedef struct vsrmc_where_info {
@@ -326,6 +326,55 @@ int32_t vsrmc_where_describe(const vsrmc_where* w, vsrmc_where_desc* out);
 int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint8_t* flags);
 int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_where_info* out);
 int32_t vsrmc_checker_where_states(vsrmc_checker* c, uint64_t* fps, uint8_t* bits, uint64_t cap, uint64_t* n);
+
+/* ---- step predicates: user-written predicates over a state AND its successor, checked on every transition (VSR.tla only) ------
+ * The safety half of PROPERTY: an action property [][P]_vars is a predicate over a (state, successor) pair.  The language of the state predicates
+ * plus primed variables (rep_view_number'[r], Len(rep_log[r])', (...)', \A m \in DOMAIN messages', messages'[m]), UNCHANGED e and step_action (the
+ * Next disjunct that produced the pair — not TLA+) — csrc/vsr_where_parse.hpp specifies it, what is refused, and where it departs from TLC: the
+ * primed aux variables are those of the successor AS GENERATED (before the search picks the representative of its VIEW class), and a pair whose
+ * successor equals its state is evaluated like any other (TLC's [][P]_vars would skip it).  Exported predicate k is bit k everywhere below.
+ * vsrmc_step_compile: needs no device.  A text without primes compiles to exactly the ops vsrmc_where_compile gives it; the program carries a step
+ *   flag (vsrmc_where_desc.step).  vsrmc_where_compile keeps refusing primes; vsrmc_where_batch / vsrmc_checker_where_scan refuse a step program
+ *   (VSRMC_E_ARG), vsrmc_step_batch / vsrmc_checker_step_scan a state program.  The same caps: 4096 ops, depth 32, 8 exports.  Destroyed and
+ *   described by vsrmc_where_destroy / vsrmc_where_describe.
+ * vsrmc_step_batch: n wire records of the caller -> one row of five words per generated successor, in (parent, ordinal) order — the rows of
+ *   vsrmc_expand_batch over the same batch, row for row: [parent, ordinal, action id, bits, error code].  An instance whose action raises an
+ *   evaluation error (error code != 0) is not evaluated: its bits are 0.  rows == NULL asks for the number.
+ * vsrmc_checker_step_scan: every transition out of the newest STORED level (csrc/vsr_step.hpp: k_step_list lists the enabled instances, k_step_apply
+ *   evaluates each pair without writing a successor).  Valid exactly where vsrmc_checker_where_scan is, with the same VSRMC_E_STATE cases, any
+ *   number of times; changes nothing a later call can observe.  n_pairs + n_err == `generated` of the step that then expands the level.  count /
+ *   min_fp are exact; min_fp[k] is the smallest PARENT fingerprint with a pair that satisfies k, min_ordinal[k] the smallest ordinal of that parent
+ *   with bit k, min_action[k] its action id: the same pair whatever the slice size and the list size.  Across runs min_fp and the counts are the same;
+ *   the ordinal is a position in the bag of the record as THIS run's level stores it (under SYMMETRY a level may store another member of the state's
+ *   orbit from run to run), so min_ordinal / min_action may name another instance of the same parent in another run.  The level is run in slices of parents sized
+ *   so that the instance list (2^22 entries) cannot overflow; the device counter is checked after every slice regardless, and a slice that
+ *   offered more is run again in halves.  (Test knob: the environment variable VSRMC_STEP_SLICE=N sets the parents per slice; it has no other use.)
+ * vsrmc_checker_step_pairs: the pairs of the last scan with any bit set, by (parent fingerprint, ordinal), their bits beside them; fps == NULL
+ *   asks for the number.  The contract of vsrmc_checker_where_states: at most 2^20 are kept, beyond that *n is the true number and the call
+ *   returns VSRMC_E_REP.  (Test knob: the environment variable VSRMC_STEP_LIST_CAP=N lowers the 2^20 to N; it has no other use.) */
+typedef struct vsrmc_step_info {
+  int32_t level, reserved0;                        /* the level scanned = the newest STORED level */
+  uint64_t n_states;                               /* parent records */
+  uint64_t n_pairs, n_err;                         /* pairs evaluated; instances whose action raises an evaluation error (not evaluated) */
+  uint64_t count[8];                               /* pairs that satisfy predicate k */
+  uint64_t min_fp[8], min_index[8];                /* the smallest parent fingerprint among them and its index in the level; ~0 if none */
+  uint32_t min_ordinal[8];                         /* of that parent, the smallest ordinal with bit k; ~0 if none */
+  int32_t min_action[8];                           /* ... and its action id; -1 if none */
+  double kernel_ms, list_ms, apply_ms;             /* HIP-event time of both kernels over all slices, and of each */
+  uint64_t slices;                                 /* launches of k_step_list (slices run again in halves included) */
+} vsrmc_step_info;
+int32_t vsrmc_step_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
+int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint64_t* rows,
+                         uint64_t cap_rows, uint64_t* n_rows);
+int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_step_info* out);
+/* the successor pair (index, ordinal) of the level of the last step scan leads to — the record as the action generates it — and its action id.  Valid
+ * while that level is the newest stored one (VSRMC_E_STATE afterwards): the ordinal names a position in the bag of the record as the level stores it.
+ * parent != NULL: a wire record of the same state (the last record of vsrmc_checker_trace_fp: under SYMMETRY it may be another member of the state's
+ * orbit than the stored one); the successor returned is then the one that record has under the same action with the same fingerprint, so that the
+ * trace and its last step are one behaviour. */
+int32_t vsrmc_checker_step_successor(vsrmc_checker* c, uint64_t index, uint32_t ordinal, const uint64_t* parent, uint64_t parent_words, uint64_t* words,
+                                     uint64_t cap_words, uint64_t* n_words, int32_t* action);
+int32_t vsrmc_checker_step_pairs(vsrmc_checker* c, uint64_t* fps, uint32_t* ordinals, uint8_t* bits, uint64_t cap, uint64_t* n);
 
 /* Probe level: expand the newest level without storing its successors — invariants are evaluated on every successor that is
  * not a state of an earlier level, nothing is inserted or written, so the level costs no frontier memory; the search cannot

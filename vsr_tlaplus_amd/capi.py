@@ -48,12 +48,18 @@ class TerminalInfo(C.Structure):
 
 class WhereDesc(C.Structure):
     _fields_ = [("n_names", C.c_int32), ("n_ops", C.c_int32), ("depth", C.c_int32), ("msg_loops", C.c_int32), ("n_bodies", C.c_int32),
-                ("reserved0", C.c_int32), ("names", (C.c_char * 64) * 8)]
+                ("step", C.c_int32), ("names", (C.c_char * 64) * 8)]
 
 
 class WhereInfo(C.Structure):
     _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8),
                 ("min_index", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
+
+
+class StepInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("n_pairs", C.c_uint64), ("n_err", C.c_uint64),
+                ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8), ("min_index", C.c_uint64 * 8), ("min_ordinal", C.c_uint32 * 8),
+                ("min_action", C.c_int32 * 8), ("kernel_ms", C.c_double), ("list_ms", C.c_double), ("apply_ms", C.c_double), ("slices", C.c_uint64)]
 
 
 class ShardIO(C.Structure):
@@ -135,6 +141,11 @@ SYMBOLS = {
     "vsrmc_where_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V]),
     "vsrmc_checker_where_scan": (C.c_int32, [V, V, C.POINTER(WhereInfo)]),
     "vsrmc_checker_where_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_step_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
+    "vsrmc_step_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_step_scan": (C.c_int32, [V, V, C.POINTER(StepInfo)]),
+    "vsrmc_checker_step_successor": (C.c_int32, [V, C.c_uint64, C.c_uint32, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "vsrmc_checker_step_pairs": (C.c_int32, [V, V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_check": (C.c_int32, [V, C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(LevelInfo)]),
     "vsrmc_queue_create": (C.c_int32, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(V)]),
     "vsrmc_queue_enqueue_batch": (C.c_int32, [V, V, V, C.c_uint64]),

@@ -28,19 +28,22 @@ def _p(a):
 
 
 class Where:
-    """State predicates compiled for one model (Model.compile_where): `names[k]` is the exported predicate of bit k."""
+    """State predicates compiled for one model (Model.compile_where), or step predicates (Model.compile_step: `step` is True; they run over
+    (state, successor) pairs): `names[k]` is the exported predicate of bit k."""
 
     def __init__(self, handle, model):
         self._h = handle
         self.model = model                                            # (keeps the model alive)
-        self.names = self.describe()["names"]
+        d = self.describe()
+        self.names, self.step = d["names"], d["step"]
 
     def describe(self):
-        """-> dict(names, n_ops, depth, msg_loops, n_bodies): the exported names, program length, operand-stack depth, nesting of the message
-        quantifiers that remain as loops, quantifier bodies after unfolding."""
+        """-> dict(names, n_ops, depth, msg_loops, n_bodies, step): the exported names, program length, operand-stack depth, nesting of the message
+        quantifiers that remain as loops, quantifier bodies after unfolding, whether it is a step program."""
         d = capi.WhereDesc()
         check(capi.load().vsrmc_where_describe(self._h, C.byref(d)))
-        return dict(names=[d.names[k].value.decode() for k in range(d.n_names)], n_ops=d.n_ops, depth=d.depth, msg_loops=d.msg_loops, n_bodies=d.n_bodies)
+        return dict(names=[d.names[k].value.decode() for k in range(d.n_names)], n_ops=d.n_ops, depth=d.depth, msg_loops=d.msg_loops, n_bodies=d.n_bodies,
+                    step=bool(d.step))
 
     def close(self):
         if self._h:
@@ -175,6 +178,27 @@ class Model:
         flags = np.zeros(max(1, n), dtype=np.uint8)
         check(capi.load().vsrmc_where_batch(self._h, device, w._h, _p(words), _p(off), n, _p(flags)))
         return flags[:n]
+
+    def compile_step(self, text):
+        """Step predicates (csrc/vsr_where_parse.hpp: the language of compile_where plus primed variables, UNCHANGED and step_action) -> Where with
+        step == True.  Needs no device.  Raises VsrmcError with "line:col: reason" for a text that is refused."""
+        h = C.c_void_p()
+        check(capi.load().vsrmc_step_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return Where(h, self)
+
+    def step_flags(self, w, words, off, device=0):
+        """The step predicates of `w` on every transition out of a batch of states (k_step_list, k_step_apply) -> an (n, 5) uint64 array, one row
+        [parent, ordinal, action, bits, err] per generated successor in (parent, ordinal) order: the rows of get_next_states, row for row.  A row
+        with err != 0 (the action raises an evaluation error) was not evaluated: bits 0."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        lib = capi.load()
+        total = C.c_uint64()
+        check(lib.vsrmc_step_batch(self._h, device, w._h, _p(words), _p(off), n, None, 0, C.byref(total)))
+        rows = np.zeros((max(1, total.value), 5), dtype=np.uint64)
+        check(lib.vsrmc_step_batch(self._h, device, w._h, _p(words), _p(off), n, _p(rows), len(rows), C.byref(total)))
+        return rows[: total.value]
 
     def tlc_fingerprints(self, words, off, device=0):
         """TLC's own fingerprint (tlc2.util.FP64 over Value.fingerPrint of `view`; [TLC-RECALLED], csrc/vsr_tlcfp.hpp) of a batch of states,
@@ -512,14 +536,18 @@ class ModelChecker:
             check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))
         return st.value
 
-    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False, reach=None, never=None):
+    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False, reach=None, never=None, step_never=None, step_reach=None):
         """Worker.run until the queue is empty, an invariant is violated, or a bound is hit — the automatic level scheme: levels are
         stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen).
         check_deadlock (TLC's default, off here): every stored level is scanned for terminal states before it is expanded; the first level
         that has one ends the run with "deadlock" — self.deadlock = the scan's result, deadlock_trace() the behaviour.
         reach / never (a Where each, off by default): every stored level is scanned (k_where) before it is expanded, where check_deadlock scans.  The
         first level with a state that satisfies a predicate of `reach` ends the run with "reached"; one that satisfies a predicate of `never` (the
-        negation of a user's invariant) ends it with "violation".  self.witness = dict(level, k, name, fp, index, kind); witness_trace() the behaviour."""
+        negation of a user's invariant) ends it with "violation".  self.witness = dict(level, k, name, fp, index, kind); witness_trace() the behaviour.
+        step_never / step_reach (a step Where each — Model.compile_step — off by default): every stored level is step-scanned (step_scan: every
+        transition out of it) before it is expanded, after the scans above.  A pair that satisfies a predicate of step_never ends the run with
+        "violation", one that satisfies step_reach with "reached"; self.witness then names the PARENT (level, fp, index) and has `ordinal` and
+        `action` besides; step_witness_trace() is the behaviour with the step at its end."""
         import time
         t0 = time.time()
         while True:
@@ -542,6 +570,16 @@ class ModelChecker:
                     if hits:
                         k = hits[0]
                         self.witness = dict(level=t["level"], k=k, name=w.names[k], fp=t["min_fp"][k], index=t["min_index"][k], kind=kind)
+                        return kind
+                for w, kind in ((step_never, "violation"), (step_reach, "reached")):
+                    if w is None:
+                        continue
+                    t = self.step_scan(w)
+                    hits = [k for k in range(len(w.names)) if t["count"][k]]
+                    if hits:
+                        k = hits[0]
+                        self.witness = dict(level=t["level"], k=k, name=w.names[k], fp=t["min_fp"][k], index=t["min_index"][k], kind=kind,
+                                            ordinal=t["min_ordinal"][k], action=ACTION_NAMES[t["min_action"][k]])
                         return kind
             kind, d, p = self.advance()
             if d["n_new"] == 0:
@@ -619,6 +657,52 @@ class ModelChecker:
         if fps[k] is None:
             raise ValueError("no state of level %d satisfies %s" % (level, w.names[k]))
         return self.trace_fp(level, fps[k])
+
+    def step_scan(self, w):
+        """Evaluate the step predicates of `w` on every transition out of the newest stored level (k_step_list / k_step_apply; no successor is
+        written, the seen-set untouched) -> dict(level, n_states, n_pairs, n_err, count[k], min_fp[k], min_index[k], min_ordinal[k], min_action[k],
+        kernel_ms, list_ms, apply_ms, slices).  min_fp[k] is the smallest PARENT fingerprint with a pair that satisfies predicate k, min_ordinal[k]
+        that parent's smallest such ordinal; None where no pair satisfies it.  n_pairs + n_err == `generated` of the step that expands the level."""
+        info = capi.StepInfo()
+        check(capi.load().vsrmc_checker_step_scan(self._h, w._h, C.byref(info)))
+        none = (1 << 64) - 1
+        n = len(w.names)
+        has = [info.count[k] != 0 for k in range(n)]
+        return dict(level=info.level, n_states=info.n_states, n_pairs=info.n_pairs, n_err=info.n_err, count=[int(info.count[k]) for k in range(n)],
+                    min_fp=[None if info.min_fp[k] == none else int(info.min_fp[k]) for k in range(n)],
+                    min_index=[None if info.min_index[k] == none else int(info.min_index[k]) for k in range(n)],
+                    min_ordinal=[int(info.min_ordinal[k]) if has[k] else None for k in range(n)],
+                    min_action=[int(info.min_action[k]) if has[k] else None for k in range(n)],
+                    kernel_ms=info.kernel_ms, list_ms=info.list_ms, apply_ms=info.apply_ms, slices=int(info.slices))
+
+    def step_pairs(self):
+        """The pairs of the last step_scan() that satisfy any predicate -> (parent fingerprints, ordinals, bits), by (fingerprint, ordinal)."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_step_pairs(self._h, None, None, None, 0, C.byref(n))
+        if rc not in (0, -5):                                             # -5 (VSRMC_E_REP): more than the list holds — raised below, by the call that copies
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        ords = np.zeros(max(1, n.value), dtype=np.uint32)
+        bits = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_step_pairs(self._h, _p(fps), _p(ords), _p(bits), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), ords[: n.value].copy(), bits[: n.value].copy()
+
+    def step_witness_trace(self):
+        """The behaviour into the pair run(step_never= / step_reach=) stopped at: trace_fp(level, parent fingerprint) plus one entry (action name,
+        successor record) — the successor as the action generated it."""
+        wit = self.witness
+        if wit is None or "ordinal" not in wit:
+            raise ValueError("run(step_never=..) / run(step_reach=..) has not stopped at a pair")
+        tr = self.trace_fp(wit["level"], wit["fp"])
+        # (the ordinal names a position in the bag of the record as the level stores it; the traced record of that state may be another member of its
+        # orbit: the library finds the same step — action and successor fingerprint — out of the traced record)
+        words = np.zeros(int(self.model.layout.max_record_words), dtype=np.uint64)
+        parent = np.ascontiguousarray(tr[-1][1], dtype=np.uint64)
+        n, act = C.c_uint64(), C.c_int32()
+        check(capi.load().vsrmc_checker_step_successor(self._h, wit["index"], wit["ordinal"], _p(parent), len(parent), _p(words), len(words), C.byref(n),
+                                                       C.byref(act)))
+        return tr + [(ACTION_NAMES[act.value], words[: n.value].copy())]
 
     def deadlock_trace(self):
         """The behaviour into the terminal state terminal_scan() / run(check_deadlock=True) reported (self.deadlock): [(action name, record)]

@@ -115,6 +115,12 @@ struct vsrmc_checker {
   std::vector<uint8_t> where_bits;
   u64 where_total = 0;
   int where_level = -1;
+  // the last vsrmc_checker_step_scan (host_step.hpp): the pairs with any predicate bit set, by (parent fingerprint, ordinal)
+  std::vector<u64> step_fps;
+  std::vector<uint32_t> step_ords;
+  std::vector<uint8_t> step_bits;
+  u64 step_total = 0;
+  int step_level = -1;
 #ifdef VSRMC_TEST_HOOKS
   // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
   std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending

@@ -63,12 +63,14 @@ int32_t vsrmc_where_describe(const vsrmc_where* w, vsrmc_where_desc* out) {
   out->depth = w->prog.depth;
   out->msg_loops = w->prog.msg_loops;
   out->n_bodies = w->prog.n_bodies;
+  out->step = w->prog.step ? 1 : 0;
   for (size_t k = 0; k < w->prog.names.size(); k++) std::snprintf(out->names[k], sizeof(out->names[k]), "%s", w->prog.names[k].c_str());
   return 0;
 }
 
 int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint8_t* flags) {
   if (!m || !w || !words || !off || !flags) return fail(VSRMC_E_ARG, "NULL argument");
+  if (w->prog.step) return fail(VSRMC_E_ARG, "state predicates: a step program (vsrmc_step_compile) runs over pairs: vsrmc_step_batch");
   if (!where_fits(w, m->M, m->symmetry)) return fail(VSRMC_E_ARG, "state predicates: compiled for another model");
   int rc = check_device(device);
   if (rc) return rc;
@@ -115,6 +117,7 @@ int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_w
   std::memset(out, 0, sizeof(*out));
   out->level = c->level;
   for (int k = 0; k < WHERE_MAX_EXPORTS; k++) out->min_fp[k] = out->min_index[k] = ~(u64)0;
+  if (w->prog.step) return fail(VSRMC_E_ARG, "state predicates: a step program (vsrmc_step_compile) runs over pairs: vsrmc_checker_step_scan");
   if (!where_fits(w, c->model.M, c->model.symmetry)) return fail(VSRMC_E_ARG, "state predicates: compiled for another model");
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "where scan: sharded checkers are not scanned");
   if (c->deep || c->deep_regen_done || c->full_recoverable)

@@ -20,7 +20,7 @@ namespace vsr {
 enum {
   W_END = 0,
   W_PUSH,      // arg: 24-bit signed immediate
-  W_LDBITS,    // arg: word(8) | shift(6) << 8 | width(6) << 14 : (rec[word] >> shift) & mask
+  W_LDBITS,    // arg: word(8) | shift(6) << 8 | width(6) << 14 | primed(1) << 20 : (rec[word] >> shift) & mask; primed (step programs only): of the child's word
   W_LDM,       // arg: loop(1) | shift(6) << 1 | width(6) << 7 : the same of the current bag word of message loop `loop`
   W_LDMENT,    // arg: loop : m.message — the entry byte of a PrepareMsg, 0 for every other type
   W_ENTF,      // arg: 0 view_number, 1 operation (value index + 1), 2 client_id, 3 request_number : field of the entry byte on top; an absent entry (0) reads 0
@@ -30,9 +30,10 @@ enum {
   W_EQ, W_NE, W_LT, W_LE, W_GT, W_GE,
   W_AND, W_OR, W_NOT, W_IMP,
   W_SEL,       // pops a, c, acc; pushes c ? a : acc
-  W_MBEGIN,    // arg: pc of the matching W_MEND (12) | loop << 12 | forall << 13
-  W_MEND,      // arg: loop | forall << 1 | pc of the first body op << 2
+  W_MBEGIN,    // arg: pc of the matching W_MEND (12) | loop << 12 | forall << 13 | primed << 14 (step programs only: the loop runs over the child's bag)
+  W_MEND,      // arg: loop | forall << 1 | pc of the first body op << 2 | primed << 14
   W_OUT,       // arg: k : pops a boolean into bit k of the result
+  W_STEPACT,   // step programs only (vsr_step.hpp): pushes the action id of the pair
   W_OPCOUNT
 };
 enum { WHERE_MAX_OPS = 4096, WHERE_MAX_DEPTH = 32, WHERE_MAX_EXPORTS = 8 };
@@ -45,14 +46,29 @@ VSR_HD u32 w_op(int code, u32 arg) { return ((u32)code << 24) | (arg & 0xFFFFFFu
 #define VSR_WHERE_UNI(x) (x)
 #endif
 
+// what a state program runs over: one record, no successor.  A step program (vsr_step.hpp) passes a pair view instead: is_pair = true, word(w) = word w
+// of the child, msg(j) = bag word j of the child, nmsg_c = the child's bag size, action = the action id.  Everything that looks at the pair is under
+// `if constexpr (PAIR::is_pair)`: k_where's instantiation contains none of it.
+struct WhereNoPair { static constexpr bool is_pair = false; };
+
 // One record through the program.  `S` is the operand stack (S[slot] -> int&); valid = the lane has a record; wmax = the largest nmsg of the lanes that
 // run together (on the host: nmsg).  Returns the exported bits.
-template <typename STACK, typename PTR>
-VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool valid, int nmsg, int wmax, STACK& S) {
+template <typename STACK, typename PTR, typename PAIR = WhereNoPair>
+VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool valid, int nmsg, int wmax, STACK& S, const PAIR& pair = PAIR()) {
   u32 bits = 0;
   int sp = 0, pc = 0;
   int j0 = 0, j1 = 0, acc0 = 0, acc1 = 0;
   u64 mw0 = 0, mw1 = 0;
+  // bag word j of the loop's bag and that bag's size, for this lane (a state program: always the record's own bag)
+  auto bag_n = [&](u32 primed) -> int {
+    if constexpr (PAIR::is_pair) return primed ? pair.nmsg_c : nmsg;
+    else { (void)primed; return nmsg; }
+  };
+  auto bag_word = [&](u32 primed, int j) -> u64 {
+    if constexpr (PAIR::is_pair) { if (primed) return (valid && j < pair.nmsg_c) ? pair.msg(j) : (u64)0; }
+    else (void)primed;
+    return (valid && j < nmsg) ? rec[fixed + j] : (u64)0;
+  };
   for (;;) {
     const u32 op = VSR_WHERE_UNI(prog[pc]);
     pc++;
@@ -61,7 +77,8 @@ VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool vali
       case W_END: return bits;
       case W_PUSH: S[sp++] = (int)(arg << 8) >> 8; break;
       case W_LDBITS: {
-        const u64 w = valid ? rec[arg & 0xFF] : (u64)0;
+        u64 w = valid ? rec[arg & 0xFF] : (u64)0;
+        if constexpr (PAIR::is_pair) { if (valid && ((arg >> 20) & 1)) w = pair.word((int)(arg & 0xFF)); }
         S[sp++] = (int)((u32)(w >> ((arg >> 8) & 63)) & (u32)((((u64)1) << ((arg >> 14) & 63)) - 1));
         break;
       }
@@ -98,29 +115,35 @@ VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool vali
       }
       case W_MBEGIN: {
         const int forall = (int)((arg >> 13) & 1);
-        if ((arg >> 12) & 1) { j1 = 0; acc1 = forall; mw1 = (valid && nmsg > 0) ? rec[fixed] : (u64)0; }
-        else { j0 = 0; acc0 = forall; mw0 = (valid && nmsg > 0) ? rec[fixed] : (u64)0; }
+        const u32 pr = (arg >> 14) & 1;
+        if ((arg >> 12) & 1) { j1 = 0; acc1 = forall; mw1 = bag_word(pr, 0); }
+        else { j0 = 0; acc0 = forall; mw0 = bag_word(pr, 0); }
         if (wmax == 0) { S[sp++] = forall; pc = (int)(arg & 0xFFF) + 1; }
         break;
       }
       case W_MEND: {
         const int forall = (int)((arg >> 1) & 1);
         const int v = S[--sp];
+        const u32 pr = (arg >> 14) & 1;
+        const int nm = bag_n(pr);
         if (arg & 1) {
-          if (j1 < nmsg) acc1 = forall ? (acc1 & v) : (acc1 | v);
+          if (j1 < nm) acc1 = forall ? (acc1 & v) : (acc1 | v);
           j1++;
-          if (j1 < wmax) { mw1 = (valid && j1 < nmsg) ? rec[fixed + j1] : (u64)0; pc = (int)(arg >> 2); }
+          if (j1 < wmax) { mw1 = bag_word(pr, j1); pc = (int)((arg >> 2) & 0xFFF); }
           else S[sp++] = acc1;
         } else {
-          if (j0 < nmsg) acc0 = forall ? (acc0 & v) : (acc0 | v);
+          if (j0 < nm) acc0 = forall ? (acc0 & v) : (acc0 | v);
           j0++;
-          if (j0 < wmax) { mw0 = (valid && j0 < nmsg) ? rec[fixed + j0] : (u64)0; pc = (int)(arg >> 2); }
+          if (j0 < wmax) { mw0 = bag_word(pr, j0); pc = (int)((arg >> 2) & 0xFFF); }
           else S[sp++] = acc0;
         }
         break;
       }
       case W_OUT: bits |= (S[--sp] ? 1u : 0u) << (arg & 7); break;
       default: {                                                    // the binary operators
+        if constexpr (PAIR::is_pair) {
+          if ((op >> 24) == W_STEPACT) { S[sp++] = pair.action; break; }
+        }
         const int b = S[--sp], a = S[sp - 1];
         int r = 0;
         switch (op >> 24) {

@@ -31,9 +31,33 @@
 //   * aux_svc and aux_client_acked are outside VIEW: of the states that differ only there the search keeps one representative (the smallest canonical
 //     auxkey), and a predicate on them sees that representative.
 //
+//   * (step predicates, below) the primed aux variables — aux_svc', aux_client_acked'[v] — are those of the successor AS THE ACTION GENERATES IT, before the
+//     search picks the representative of its VIEW class: a pair is (stored state, generated successor), not (stored state, stored state).
+//
 // Refused (code 1 = VSRMC_E_ARG, message "line:col: reason"): unknown identifier, unbound variable, forward or recursive reference, type mismatch
 // (rep_status[r] = 1), primes, temporal operators, CHOOSE, LAMBDA, set constructors, a quantifier over any other set, more than 8 exported names.
 // Code 2 = VSRMC_E_REP: a program beyond 4096 ops or an operand depth beyond 32.
+//
+// STEP PREDICATES (where_compile(.., step = true); vsrmc_step_compile): predicates over a state and its successor — the safety half of PROPERTY, an action
+// property [][P]_vars — evaluated on every transition the checker generates (vsr_step.hpp).  The same grammar plus:
+//   prime        ' after a state variable name (rep_view_number'[r], rep_log'[r][i].operation, messages', aux_svc') and after a primary expression
+//                (rep_view_number[r]', Len(rep_log[r])', (...)'): every state variable inside the primed expression is read in the successor; bound
+//                variables and constants are what they are.  A double prime, and a prime on an expression that contains one (directly or through a
+//                definition), are refused.
+//   messages     \A m \in DOMAIN messages' : ... quantifies over the successor's bag, and messages'[m] is the successor's count for such an m.  At most two
+//                nested message quantifiers, in any mix of bags.  A message bound over one bag as a key of the other — messages'[m] with m from DOMAIN
+//                messages, m \in DOMAIN messages' as a test — would need a search of the bag and is refused.
+//   UNCHANGED e  == (e' = e), for any e that can be compared with = (integers, booleans, statuses, values, log entries), for rep_log[r], and for the whole
+//                per-replica variables rep_status, rep_view_number, rep_op_number, rep_commit_number, rep_last_normal_view and rep_log, where it unfolds
+//                over replicas.  UNCHANGED of any other whole variable (messages, rep_client_table, ...) is refused.
+//   step_action  NOT TLA+: the Next disjunct that produced the pair.  A type of its own, comparable with = / # against the fifteen action names as traces
+//                print them (TimerSendSVC ReceiveHigherSVC ReceiveMatchingSVC SendDVC ReceiveHigherDVC ReceiveMatchingDVC SendSV ReceiveSV
+//                ReceiveClientRequest ReceivePrepareMsg ReceivePrepareOkMsg ExecuteOp SendGetState ReceiveGetState ReceiveNewState).  TLA+ cannot name the
+//                disjunct of a step; a property that needs it there restates the action's guard.
+// Everything else keeps its meaning on both sides of a pair, the defined results of out-of-domain accesses included.  A pair whose successor equals its
+// state is evaluated like any other (TLC's [][P]_vars would skip a stuttering step).  A text without primes compiles to exactly the ops the state entry
+// gives it; the state entry (step = false) keeps refusing primes, UNCHANGED and step_action.  Still out of scope: temporal operators, fairness, ENABLED,
+// PROPERTY / ACTION_CONSTRAINT sections of a cfg.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -52,6 +76,7 @@ struct WhereProgram {
   std::vector<u32> ops;
   std::vector<std::string> names;      // exported, bit k = names[k]
   int depth = 0, msg_loops = 0, n_bodies = 0;
+  bool step = false;                   // compiled by step_compile: runs over (state, successor) pairs (vsr_step.hpp), refused by k_where's entry points
 };
 
 namespace where_detail {
@@ -59,8 +84,8 @@ namespace where_detail {
 struct Err { int code; std::string msg; };
 enum { TK_EOF, TK_ID, TK_NUM, TK_OP };
 struct Tok { int kind; std::string s; long v; int line, col; };
-enum { TY_INT, TY_BOOL, TY_STATUS, TY_MTYPE, TY_VALUE, TY_ENTRY };
-enum { N_NUM, N_BOOL, N_ID, N_NOT, N_NEG, N_BIN, N_QUANT, N_INDEX, N_FIELD, N_CALL, N_DOMAIN };
+enum { TY_INT, TY_BOOL, TY_STATUS, TY_MTYPE, TY_VALUE, TY_ENTRY, TY_ACTION };
+enum { N_NUM, N_BOOL, N_ID, N_NOT, N_NEG, N_BIN, N_QUANT, N_INDEX, N_FIELD, N_CALL, N_DOMAIN, N_PRIME, N_UNCHANGED };
 struct Node;
 typedef std::shared_ptr<Node> NodeP;
 struct Node {
@@ -77,7 +102,7 @@ struct Node {
   throw Err{code, std::to_string(line) + ":" + std::to_string(col) + ": " + why};
 }
 inline const char* type_name(int t) {
-  static const char* const N[] = {"an integer", "a boolean", "a status", "a message type", "a value", "a log entry"};
+  static const char* const N[] = {"an integer", "a boolean", "a status", "a message type", "a value", "a log entry", "an action"};
   return N[t];
 }
 
@@ -143,6 +168,7 @@ inline std::vector<Tok> lex(const std::string& t) {
 struct Parser {
   std::vector<Tok> t;
   size_t p = 0;
+  bool step = false;                                            // a step predicate: ' and UNCHANGED are part of the language
   const Tok& peek(size_t a = 0) const { return t[std::min(p + a, t.size() - 1)]; }
   bool is_op(const char* s, size_t a = 0) const { return peek(a).kind == TK_OP && peek(a).s == s; }
   bool is_id(const char* s) const { return peek().kind == TK_ID && peek().s == s; }
@@ -168,15 +194,17 @@ struct Parser {
   void refuse_unsupported(const Tok& k) const {
     if (k.kind == TK_OP) {
       const std::string& s = k.s;
-      if (s == "'") fail(k, "primed variables are not part of a state predicate");
-      if (s == "[]" || s == "<>" || s == "~>") fail(k, "temporal operators are not part of a state predicate");
+      if (s == "'" && !step) fail(k, "primed variables are not part of a state predicate");
+      if (s == "[]" || s == "<>" || s == "~>") fail(k, step ? "temporal operators are not part of a step predicate" : "temporal operators are not part of a state predicate");
       if (s == "{" || s == "<<" || s == "|->" || s == "\\cup" || s == "\\cap" || s == "\\union" || s == "\\intersect" || s == "\\subseteq" || s == "\\X" || s == "\\times")
         fail(k, "set, tuple and record constructors are not supported");
       if (s == "\\notin") fail(k, "\\notin is not supported: write ~(x \\in S)");
     } else if (k.kind == TK_ID) {
       const std::string& s = k.s;
       if (s == "CHOOSE" || s == "LAMBDA") fail(k, s + " is not supported");
-      if (s == "ENABLED" || s == "UNCHANGED" || s == "WF_vars" || s == "SF_vars") fail(k, s + ": action and temporal operators are not part of a state predicate");
+      if (step && s == "UNCHANGED") return;
+      if (s == "ENABLED" || s == "UNCHANGED" || s == "WF_vars" || s == "SF_vars")
+        fail(k, s + (step ? ": not part of a step predicate" : ": action and temporal operators are not part of a state predicate"));
       if (s == "IF" || s == "THEN" || s == "ELSE" || s == "LET" || s == "IN" || s == "CASE" || s == "SUBSET" || s == "UNION" || s == "EXCEPT") fail(k, s + " is not supported");
     }
   }
@@ -222,6 +250,7 @@ struct Parser {
       return n;
     }
     if (is_id("DOMAIN")) { p++; NodeP n = mk(N_DOMAIN, k); n->c = {postfix()}; return n; }
+    if (step && is_id("UNCHANGED")) { p++; NodeP n = mk(N_UNCHANGED, k); n->c = {unary()}; return n; }
     return postfix();
   }
   NodeP postfix() {
@@ -244,6 +273,11 @@ struct Parser {
         n = f;
       } else if (is_op("'")) {
         refuse_unsupported(k);
+        if (n->k == N_PRIME) fail(k, "double prime");
+        p++;
+        NodeP pr = mk(N_PRIME, k);
+        pr->c = {n};
+        n = pr;
       } else {
         return n;
       }
@@ -275,7 +309,7 @@ struct Parser {
   }
 };
 
-struct Binding { std::string name; int kind; int v; };       // kind 0: integer constant, 1: value constant (index + 1), 2: message loop v
+struct Binding { std::string name; int kind; int v; bool primed = false; };   // kind 0: integer constant, 1: value constant (index + 1), 2: message loop v (primed: over messages')
 struct Def { NodeP body; };
 
 struct Compiler {
@@ -287,6 +321,8 @@ struct Compiler {
   std::map<std::string, Def> defs;
   std::string compiling;                                      // the definition being compiled (recursion)
   int cur = 0, msg_depth = 0;
+  bool step = false;                                          // a step predicate: step_action and the action names exist
+  bool P = false;                                             // the loads being emitted read the successor (inside a primed expression)
 
   Compiler(const Model& m, bool sym, const std::vector<std::string>& vals, WhereProgram& o) : M(m), symmetry(sym), values(vals), out(o) {}
 
@@ -298,7 +334,7 @@ struct Compiler {
     if (cur > (int)WHERE_MAX_DEPTH) throw Err{2, "state predicates: operand depth beyond " + std::to_string((int)WHERE_MAX_DEPTH)};
   }
   void push(int v) { emit(W_PUSH, (u32)v & 0xFFFFFFu, +1); }
-  void ldbits(int word, int shift, int width) { emit(W_LDBITS, (u32)word | ((u32)shift << 8) | ((u32)width << 14), +1); }
+  void ldbits(int word, int shift, int width) { emit(W_LDBITS, (u32)word | ((u32)shift << 8) | ((u32)width << 14) | ((u32)P << 20), +1); }
   void ldm(int loop, int shift, int width) { emit(W_LDM, (u32)loop | ((u32)shift << 1) | ((u32)width << 7), +1); }
   void bin(int code) { emit(code, 0, -1); }
   int aword(int r) const { return 1 + (r - 1) * M.wpr; }
@@ -354,14 +390,15 @@ struct Compiler {
 
   // f[i1][i2]..: every index is a constant, or becomes a select chain over its candidates lo..hi.  `leaf` emits the load for one tuple of constants.
   struct Ix { NodeP n; int lo, hi, type; };
-  void indexed(const std::vector<Ix>& ixs, size_t at, std::vector<int>& vals, int deflt, const std::function<void(const std::vector<int>&)>& leaf) {
-    if (at == ixs.size()) { leaf(vals); return; }
+  // lp: the leaf loads read the successor (f'[i]: the variable is primed, the index expressions are whatever the context is)
+  void indexed(const std::vector<Ix>& ixs, size_t at, std::vector<int>& vals, int deflt, const std::function<void(const std::vector<int>&)>& leaf, bool lp) {
+    if (at == ixs.size()) { const bool saved = P; P = lp; leaf(vals); P = saved; return; }
     const Ix& x = ixs[at];
     int v;
     if (x.type == TY_INT ? const_int(x.n, &v) : const_value(x.n, &v)) {
       if (v < x.lo || v > x.hi) { push(deflt); return; }
       vals.push_back(v);
-      indexed(ixs, at + 1, vals, deflt, leaf);
+      indexed(ixs, at + 1, vals, deflt, leaf, lp);
       vals.pop_back();
       return;
     }
@@ -371,7 +408,7 @@ struct Compiler {
       push(k);
       bin(W_EQ);
       vals.push_back(k);
-      indexed(ixs, at + 1, vals, deflt, leaf);
+      indexed(ixs, at + 1, vals, deflt, leaf, lp);
       vals.pop_back();
       emit(W_SEL, 0, -2);
     }
@@ -386,28 +423,43 @@ struct Compiler {
     }
     return n;
   }
+  // v' with v a state variable: the bare name, *primed set.  (A prime further out is the context's P.)
+  NodeP strip_prime(NodeP root, bool* primed) const {
+    *primed = false;
+    if (root->k == N_PRIME && root->c[0]->k == N_ID && !lookup(root->c[0]->s) && !defs.count(root->c[0]->s)) {
+      if (P) fail(root, "double prime: " + root->c[0]->s + "' inside an expression that is primed");
+      *primed = true;
+      return root->c[0];
+    }
+    return root;
+  }
   int entry_field(const NodeP& at, const std::string& f) {
     const int k = f == "view_number" ? 0 : f == "operation" ? 1 : f == "client_id" ? 2 : f == "request_number" ? 3 : -1;
     if (k < 0) fail(at, "a log entry has no field " + f + " (view_number, operation, client_id, request_number)");
     emit(W_ENTF, (u32)k, 0);
     return k == 1 ? TY_VALUE : TY_INT;
   }
-  void emit_log_len(const NodeP& r) {                          // Len(rep_log[r])
+  void emit_log_len(const NodeP& r, bool lp) {                 // Len(rep_log[r])
     std::vector<int> vals;
-    indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); emit(W_LOGLEN, 0, 0); });
+    indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); emit(W_LOGLEN, 0, 0); }, lp);
   }
-  // rep_log[r] as the argument of Len / DOMAIN: returns the index node r
-  NodeP log_of(const NodeP& n) const {
+  // rep_log[r] / rep_log'[r] as the argument of Len / DOMAIN: returns the index node r; *lp = the log is the successor's
+  NodeP log_of(const NodeP& n, bool* lp) const {
     std::vector<Acc> acc;
+    bool pr = false;
     NodeP root = flatten(n, acc);
+    if (root->k == N_PRIME && root->c[0]->k == N_ID && root->c[0]->s == "rep_log") root = strip_prime(root, &pr);
+    *lp = P || pr;
     if (root->k == N_ID && root->s == "rep_log" && !lookup("rep_log") && acc.size() == 1 && !acc[0].field) return acc[0].ix;
     return nullptr;
   }
 
   int compile_path(const NodeP& n) {
     std::vector<Acc> acc;
-    NodeP root = flatten(n, acc);
+    bool root_primed = false;
+    NodeP root = strip_prime(flatten(n, acc), &root_primed);
     if (root->k != N_ID) fail(n, "only state variables and bound messages can be indexed or have fields");
+    const bool lp = P || root_primed;
     const std::string& s = root->s;
     auto shape = [&](std::initializer_list<bool> fields) {     // the accessors must be exactly: index (false) / field (true) in this order
       if (acc.size() != fields.size()) return false;
@@ -417,6 +469,7 @@ struct Compiler {
     };
     std::vector<int> vals;
     if (const Binding* b = lookup(s)) {
+      if (root_primed) fail(n, s + " is a bound variable: it cannot be primed");
       if (b->kind != 2) fail(n, s + " is not a message: it has no fields and cannot be indexed");
       const int d = b->v;
       if (!acc[0].field) fail(acc[0].at, "a message cannot be indexed");
@@ -441,6 +494,9 @@ struct Compiler {
       if (!shape({false})) fail(n, "messages[m] with m bound over DOMAIN messages is the supported form");
       const Binding* b = acc[0].ix->k == N_ID ? lookup(acc[0].ix->s) : nullptr;
       if (!b || b->kind != 2) fail(acc[0].ix, "messages[m]: m must be a variable bound over DOMAIN messages");
+      if (b->primed != lp)
+        fail(acc[0].ix, lp ? "messages'[" + b->name + "]: " + b->name + " is bound over DOMAIN messages, not DOMAIN messages' (a lookup in the other bag is not supported)"
+                           : "messages[" + b->name + "]: " + b->name + " is bound over DOMAIN messages', not DOMAIN messages (a lookup in the other bag is not supported)");
       ldm(b->v, 21, 2);
       return TY_INT;
     }
@@ -450,13 +506,13 @@ struct Compiler {
     for (const auto& e : A)
       if (s == e.name) {
         if (!shape({false})) fail(n, s + "[r] is the supported form");
-        indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, e.type == TY_BOOL ? 0 : -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), e.shift, e.width); });
+        indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, e.type == TY_BOOL ? 0 : -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), e.shift, e.width); }, lp);
         return e.type;
       }
     if (s == "rep_peer_op_number") {
       if (!shape({false, false})) fail(n, "rep_peer_op_number[r][p] is the supported form");
       indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, M.R, TY_INT}}, 0, vals, -1,
-              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 19 + 2 * (v[1] - 1), 2); });
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 19 + 2 * (v[1] - 1), 2); }, lp);
       return TY_INT;
     }
     if (s == "rep_client_table") {
@@ -465,18 +521,18 @@ struct Compiler {
       const int off = f == "request_number" ? 0 : f == "op_number" ? 2 : f == "executed" ? 4 : -1;
       if (off < 0) fail(acc[2].at, "a client-table row has no field " + f);
       indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, M.C, TY_INT}}, 0, vals, off == 4 ? 0 : -1,
-              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 29 + 5 * (v[1] - 1) + off, off == 4 ? 1 : 2); });
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 29 + 5 * (v[1] - 1) + off, off == 4 ? 1 : 2); }, lp);
       return off == 4 ? TY_BOOL : TY_INT;
     }
     if (s == "rep_log") {
       if (!shape({false, false}) && !shape({false, false, true})) fail(n, "rep_log[r][i], its fields, Len(rep_log[r]) and DOMAIN rep_log[r] are the supported forms");
       indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, 3, TY_INT}}, 0, vals, 0,      // outside the log: the absent entry
-              [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 8 * (v[1] - 1), 8); });
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 8 * (v[1] - 1), 8); }, lp);
       return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
     }
     if (s == "aux_client_acked") {
       if (!shape({false})) fail(n, "aux_client_acked[v] is the supported form");
-      indexed({Ix{acc[0].ix, 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(2); bin(W_EQ); });
+      indexed({Ix{acc[0].ix, 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(2); bin(W_EQ); }, lp);
       return TY_BOOL;
     }
     if (s == "rep_svc_recv" || s == "rep_dvc_recv") fail(n, s + ": only Cardinality(" + s + "[r]) is supported");
@@ -507,6 +563,7 @@ struct Compiler {
     const std::string& name = n->vars[var];
     int lo, hi, kind;
     NodeP logr;
+    bool loglp = false;
     if (const_set(set, &lo, &hi, &kind)) {
       if (lo > hi) { push(forall); return TY_BOOL; }
       for (int k = lo; k <= hi; k++) {
@@ -517,10 +574,10 @@ struct Compiler {
       }
       return TY_BOOL;
     }
-    if (set->k == N_DOMAIN && (logr = log_of(set->c[0]))) {    // 1..Len(rep_log[r]): unfolded over the three positions, each guarded by its presence
+    if (set->k == N_DOMAIN && (logr = log_of(set->c[0], &loglp))) {    // 1..Len(rep_log[r]): unfolded over the three positions, each guarded by its presence
       for (int k = 1; k <= 3; k++) {
         push(k);
-        emit_log_len(logr);
+        emit_log_len(logr, loglp);
         bin(W_LE);
         env.push_back(Binding{name, 0, k});
         compile_quant(n, var + 1);
@@ -530,21 +587,67 @@ struct Compiler {
       }
       return TY_BOOL;
     }
-    if (set->k == N_DOMAIN && set->c[0]->k == N_ID && set->c[0]->s == "messages" && !lookup("messages")) {
+    bool bagp = false;
+    const NodeP bag = set->k == N_DOMAIN ? strip_prime(set->c[0], &bagp) : nullptr;
+    if (bag && bag->k == N_ID && bag->s == "messages" && !lookup("messages")) {
       if (msg_depth >= 2) fail(n, "at most two nested quantifiers over DOMAIN messages");
+      const bool pr = P || bagp;                                  // DOMAIN messages': the successor's bag
       const int d = msg_depth++;
       if (msg_depth > out.msg_loops) out.msg_loops = msg_depth;
       const size_t begin = out.ops.size();
       emit(W_MBEGIN, 0, 0);
-      env.push_back(Binding{name, 2, d});
+      env.push_back(Binding{name, 2, d, pr});
       compile_quant(n, var + 1);
       env.pop_back();
-      out.ops[begin] = w_op(W_MBEGIN, (u32)out.ops.size() | ((u32)d << 12) | ((u32)forall << 13));
-      emit(W_MEND, (u32)d | ((u32)forall << 1) | ((u32)(begin + 1) << 2), 0);
+      out.ops[begin] = w_op(W_MBEGIN, (u32)out.ops.size() | ((u32)d << 12) | ((u32)forall << 13) | ((u32)pr << 14));
+      emit(W_MEND, (u32)d | ((u32)forall << 1) | ((u32)(begin + 1) << 2) | ((u32)pr << 14), 0);
       msg_depth--;
       return TY_BOOL;
     }
     fail(set, "a quantifier ranges over replicas, clients, Values, a..b, DOMAIN rep_log[r] or DOMAIN messages");
+  }
+
+  // UNCHANGED e == (e' = e).  A whole per-replica variable unfolds over replicas.
+  int compile_unchanged(const NodeP& n) {
+    const NodeP& e = n->c[0];
+    if (P) fail(n, "UNCHANGED inside a primed expression (it contains a prime itself)");
+    if (e->k == N_ID && !lookup(e->s) && !defs.count(e->s)) {
+      static const struct { const char* name; int word, shift, width; } V[] = {{"rep_status", 0, 0, 2}, {"rep_view_number", 0, 2, 3}, {"rep_op_number", 0, 5, 2},
+                                                                                 {"rep_commit_number", 0, 7, 2}, {"rep_last_normal_view", 0, 9, 3}, {"rep_log", 1, 0, 24}};
+      for (const auto& v : V)
+        if (e->s == v.name) {
+          for (int r = 1; r <= M.R; r++) {
+            P = true;
+            ldbits(aword(r) + v.word, v.shift, v.width);
+            P = false;
+            ldbits(aword(r) + v.word, v.shift, v.width);
+            bin(W_EQ);
+            if (r > 1) bin(W_AND);
+          }
+          return TY_BOOL;
+        }
+      static const char* const OTHER[] = {"rep_sent_dvc", "rep_sent_sv", "rep_peer_op_number", "rep_client_table", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};
+      for (const char* o : OTHER)
+        if (e->s == o)
+          fail(e, "UNCHANGED " + e->s + ": a whole variable can be rep_status, rep_view_number, rep_op_number, rep_commit_number, rep_last_normal_view or rep_log; "
+                  "apply UNCHANGED to an element otherwise");
+    }
+    bool lp = false;
+    if (NodeP r = log_of(e, &lp)) {                             // UNCHANGED rep_log[r]: the whole log of one replica
+      if (lp) fail(e, "double prime: UNCHANGED of a primed log");
+      std::vector<int> vals;
+      indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); }, true);
+      indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); }, false);
+      bin(W_EQ);
+      return TY_BOOL;
+    }
+    P = true;
+    const int a = compile(e);
+    P = false;
+    const int b = compile(e);
+    if (a != b) fail(n, "UNCHANGED: the two sides have different types");
+    bin(W_EQ);
+    return TY_BOOL;
   }
 
   int compile(const NodeP& n) {
@@ -554,6 +657,20 @@ struct Compiler {
       case N_NOT: want(n->c[0], compile(n->c[0]), TY_BOOL); emit(W_NOT, 0, 0); return TY_BOOL;
       case N_NEG: push(0); want(n->c[0], compile(n->c[0]), TY_INT); bin(W_SUB); return TY_INT;
       case N_QUANT: return compile_quant(n, 0);
+      case N_PRIME: {                                           // e': every state variable inside e is the successor's; bound variables and constants are what they are
+        if (P) fail(n, "double prime: a primed expression inside an expression that is primed");
+        if (n->c[0]->k == N_ID && !lookup(n->c[0]->s) && !defs.count(n->c[0]->s)) {
+          static const char* const FN[] = {"rep_status", "rep_view_number", "rep_op_number", "rep_commit_number", "rep_last_normal_view", "rep_sent_dvc", "rep_sent_sv",
+                                           "rep_peer_op_number", "rep_client_table", "rep_log", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};
+          for (const char* e : FN)
+            if (n->c[0]->s == e) fail(n, n->c[0]->s + "' is a function: apply it to an index");
+        }
+        P = true;
+        const int t = compile(n->c[0]);
+        P = false;
+        return t;
+      }
+      case N_UNCHANGED: return compile_unchanged(n);
       case N_INDEX:
       case N_FIELD: return compile_path(n);
       case N_DOMAIN: fail(n, "DOMAIN is supported after \\in only (DOMAIN rep_log[r], DOMAIN messages, DOMAIN aux_client_acked)");
@@ -562,13 +679,16 @@ struct Compiler {
         int v;
         if (const_int(n, &v)) { push(v); return TY_INT; }
         if (n->s == "Len") {
-          NodeP r = log_of(a);
+          bool lp = false;
+          NodeP r = log_of(a, &lp);
           if (!r) fail(n, "Len(rep_log[r]) is the supported form");
-          emit_log_len(r);
+          emit_log_len(r, lp);
           return TY_INT;
         }
         std::vector<Acc> acc;
-        NodeP root = flatten(a, acc);
+        bool rp = false;
+        NodeP root = strip_prime(flatten(a, acc), &rp);
+        const bool lp = P || rp;
         if (root->k == N_ID && !lookup(root->s) && acc.size() == 1 && !acc[0].field && (root->s == "rep_svc_recv" || root->s == "rep_dvc_recv")) {
           const bool svc = root->s == "rep_svc_recv";
           std::vector<int> vals;
@@ -578,7 +698,7 @@ struct Compiler {
               ldbits(aword(r[0]) + 1 + (s >> 1), 32 * (s & 1), 1);
               if (s > 1) bin(W_ADD);
             }
-          });
+          }, lp);
           return TY_INT;
         }
         fail(n, "Cardinality(Values), Cardinality(rep_svc_recv[r]) and Cardinality(rep_dvc_recv[r]) are the supported forms");
@@ -616,6 +736,14 @@ struct Compiler {
           return TY_VALUE;
         }
         if (s == "aux_svc") { ldbits(0, 8, 3); return TY_INT; }
+        if (step) {                                             // not TLA+: the Next disjunct that produced the pair, and the names traces print
+          if (s == "step_action") { emit(W_STEPACT, 0, +1); return TY_ACTION; }
+          static const char* const ACT[] = {"TimerSendSVC", "ReceiveHigherSVC", "ReceiveMatchingSVC", "SendDVC", "ReceiveHigherDVC", "ReceiveMatchingDVC", "SendSV",
+                                            "ReceiveSV", "ReceiveClientRequest", "ReceivePrepareMsg", "ReceivePrepareOkMsg", "ExecuteOp", "SendGetState", "ReceiveGetState",
+                                            "ReceiveNewState"};
+          for (int a = 0; a < 15; a++)
+            if (s == ACT[a]) { push(a + 1); return TY_ACTION; }
+        }
         static const char* const STATE[] = {"rep_status", "rep_view_number", "rep_op_number", "rep_commit_number", "rep_last_normal_view", "rep_sent_dvc", "rep_sent_sv",
                                             "rep_peer_op_number", "rep_client_table", "rep_log", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};
         for (const char* e : STATE)
@@ -658,11 +786,15 @@ struct Compiler {
           const NodeP& set = n->c[1];
           int lo, hi, kind;
           NodeP logr;
-          if (set->k == N_DOMAIN && set->c[0]->k == N_ID && set->c[0]->s == "aux_client_acked" && !lookup("aux_client_acked")) {
+          bool domp = false, loglp = false;
+          const NodeP dom = set->k == N_DOMAIN ? strip_prime(set->c[0], &domp) : nullptr;
+          if (dom && dom->k == N_ID && dom->s == "aux_client_acked" && !lookup("aux_client_acked")) {
             std::vector<int> vals;
-            indexed({Ix{n->c[0], 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(0); bin(W_NE); });
+            indexed({Ix{n->c[0], 1, M.n, TY_VALUE}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(0, 11 + 2 * (v[0] - 1), 2); push(0); bin(W_NE); }, P || domp);
             return TY_BOOL;
           }
+          if (dom && dom->k == N_ID && dom->s == "messages" && !lookup("messages"))
+            fail(set, "\\in DOMAIN messages as a test would search the bag: quantify over it instead (a message of one bag cannot be looked up in the other)");
           if (const_set(set, &lo, &hi, &kind)) {
             want(n->c[0], compile(n->c[0]), kind ? TY_VALUE : TY_INT);
             push(lo); bin(W_GE);
@@ -671,11 +803,11 @@ struct Compiler {
             bin(W_AND);
             return TY_BOOL;
           }
-          if (set->k == N_DOMAIN && (logr = log_of(set->c[0]))) {
+          if (set->k == N_DOMAIN && (logr = log_of(set->c[0], &loglp))) {
             want(n->c[0], compile(n->c[0]), TY_INT);
             push(1); bin(W_GE);
             compile(n->c[0]);
-            emit_log_len(logr);
+            emit_log_len(logr, loglp);
             bin(W_LE);
             bin(W_AND);
             return TY_BOOL;
@@ -693,13 +825,16 @@ struct Compiler {
 }  // namespace where_detail
 
 // 0 = compiled; 1 = refused (VSRMC_E_ARG), 2 = beyond a cap (VSRMC_E_REP): *err says why
-inline int where_compile(const Model& M, bool symmetry, const std::vector<std::string>& value_names, const std::string& text, WhereProgram* out, std::string* err) {
+inline int where_compile(const Model& M, bool symmetry, const std::vector<std::string>& value_names, const std::string& text, WhereProgram* out, std::string* err,
+                         bool step = false) {
   using namespace where_detail;
   *out = WhereProgram();
   try {
     Parser P;
+    P.step = step;
     P.t = lex(text);
     Compiler C(M, symmetry, value_names, *out);
+    C.step = step;
     bool has_defs = false;
     for (const Tok& k : P.t) has_defs = has_defs || (k.kind == TK_OP && k.s == "==");
     auto export_top = [&](const std::string& name, const Tok& at) {
@@ -725,6 +860,7 @@ inline int where_compile(const Model& M, bool symmetry, const std::vector<std::s
         if (local) {                                            // type-checked where it is used; checked here too, its code discarded
           WhereProgram scratch;
           Compiler T(M, symmetry, value_names, scratch);
+          T.step = step;
           T.defs = C.defs;
           T.compiling = name.s;
           T.compile(e);
@@ -739,6 +875,7 @@ inline int where_compile(const Model& M, bool symmetry, const std::vector<std::s
       if (out->names.empty()) fail_at(1, 1, "no exported definition");
     }
     C.emit(W_END, 0, 0);
+    out->step = step;
   } catch (const Err& e) {
     *err = e.msg;
     *out = WhereProgram();

@@ -25,6 +25,7 @@
 #include "vsr_terminal.hpp"
 #include "vsr_where.hpp"
 #include "vsr_where_parse.hpp"
+#include "vsr_step.hpp"
 
 #define VSRMC_FP_VERSION 2          // fingerprint function of this build; checkpoints of another version are refused
 
@@ -118,4 +119,5 @@ extern "C" {
 #include "host_tlcfp.hpp"        // TLC's FP64 as a mode
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
+#include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

@@ -6,7 +6,8 @@
 // -checkDeadlock to stop at the first state without successors like stock TLC would: the newest level is scanned for terminal states before it is
 // expanded (vsrmc_checker_terminal_scan) and the behaviour into the one with the smallest fingerprint is printed.  -terminalReport scans every
 // stored level without stopping.  -predicates FILE with -reach / -invariant / -whereReport evaluates the user's own state predicates (k_where) on every
-// stored level, where -checkDeadlock scans.
+// stored level, where -checkDeadlock scans.  -steps FILE with -stepReach / -stepInvariant / -stepReport does the same for step predicates (primed variables:
+// csrc/vsr_step.hpp) over every transition out of every stored level.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +42,13 @@ static void usage() {
       "  -invariant NAME[,NAME]  the same scan for ~NAME: a state in which NAME is false is reported like a violation of a built-in invariant (exit 12)\n"
       "  -whereReport      count the states that satisfy each exported predicate, level by level, without stopping; with -json a \"where\" object in\n"
       "                    the level lines.  Levels that are never stored (the Virtual / Probe lines) are not examined, and the report says how many\n"
+      "  -steps FILE       step predicates (the same language plus primed variables, UNCHANGED and step_action; an example: tools/steps_example.txt), evaluated\n"
+      "                    on every transition out of every stored level (a file of its own: -predicates FILE goes through the state compiler).  Used by:\n"
+      "  -stepInvariant NAME[,NAME]  a transition on which NAME is false ends the run: \"Error: Action property NAME is violated.\", the behaviour with\n"
+      "                    that step at its end and the step's action name (exit 12; -dumpTrace tla FILE writes it, -json adds a line)\n"
+      "  -stepReach NAME[,NAME]      the same scan for NAME itself: exit 0 when a transition satisfies it, 14 when the search ended without one\n"
+      "  -stepReport       per level the pairs, the instances that raise an evaluation error and the pairs that satisfy each exported name, without\n"
+      "                    stopping; with -json a \"steps\" object in the level lines.  Levels that are never stored are not examined, and the report says how many\n"
       "  -maxDepth N       stop after N BFS levels (Init = level 1)\n"
       "  -device D         HIP device ordinal (default 0)\n"
       "  -gpus N           N > 1: run the sharded checker on N GPUs of this node (re-executes as\n"
@@ -129,8 +137,8 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 int main(int argc, char** argv) {
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) return exec_sharded(argc, argv, i);
-  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg;
-  bool where_report = false;
+  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, steps_file, step_reach_arg, step_invariant_arg;
+  bool where_report = false, step_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
   bool check_deadlock = false, no_tla = false, json = false, simulate = false, host_frontier = false, probe_last = false, coverage = false, audit = false, terminal_report = false;
@@ -178,6 +186,10 @@ int main(int argc, char** argv) {
     else if (a == "-reach" && i + 1 < argc) reach_arg = argv[++i];
     else if (a == "-invariant" && i + 1 < argc) invariant_arg = argv[++i];
     else if (a == "-whereReport") where_report = true;
+    else if (a == "-steps" && i + 1 < argc) steps_file = argv[++i];
+    else if (a == "-stepReach" && i + 1 < argc) step_reach_arg = argv[++i];
+    else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
+    else if (a == "-stepReport") step_report = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -276,6 +288,57 @@ int main(int argc, char** argv) {
   vsrmc_where *w_all = nullptr, *w_query = nullptr;
   std::vector<std::string> where_names, query_names;
   size_t n_reach = 0;
+  auto split_names = [](const std::string& arg, std::vector<std::string>& out) {
+    std::stringstream ss(arg);
+    std::string name;
+    while (std::getline(ss, name, ','))
+      if (!name.empty()) out.push_back(name);
+  };
+  auto make_local = [](const std::string& text) {               // every `Name ==` that is not LOCAL already gets the word in front
+    std::string local;
+    for (size_t i = 0; i < text.size(); i++) {
+      if (text.compare(i, 2, "==") == 0 && (i == 0 || text[i - 1] != '=') && (i + 2 >= text.size() || text[i + 2] != '=')) {
+        size_t e = local.size();
+        while (e > 0 && std::isspace((unsigned char)local[e - 1])) e--;
+        size_t b = e;
+        while (b > 0 && (std::isalnum((unsigned char)local[b - 1]) || local[b - 1] == '_')) b--;
+        size_t q = b;
+        while (q > 0 && std::isspace((unsigned char)local[q - 1])) q--;
+        if (b < e && !(q >= 5 && local.compare(q - 5, 5, "LOCAL") == 0)) local.insert(b, "LOCAL ");
+      }
+      local.push_back(text[i]);
+    }
+    return local;
+  };
+  // step predicates (-steps FILE): the same two programs over pairs
+  vsrmc_where *s_all = nullptr, *s_query = nullptr;
+  std::vector<std::string> step_names, step_query_names;
+  size_t n_step_reach = 0;
+  if (!step_reach_arg.empty() || !step_invariant_arg.empty() || step_report) {
+    if (steps_file.empty()) { std::fprintf(stderr, "Error: -stepReach / -stepInvariant / -stepReport need -steps FILE\n"); return 2; }
+    std::ifstream pf(steps_file, std::ios::binary);
+    if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", steps_file.c_str()); return 1; }
+    std::stringstream pss;
+    pss << pf.rdbuf();
+    const std::string text = pss.str();
+    if (vsrmc_step_compile(m, text.c_str(), &s_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", steps_file.c_str(), vsrmc_last_error()); return 1; }
+    vsrmc_where_desc wd;
+    vsrmc_where_describe(s_all, &wd);
+    for (int k = 0; k < wd.n_names; k++) step_names.push_back(wd.names[k]);
+    split_names(step_reach_arg, step_query_names);
+    n_step_reach = step_query_names.size();
+    split_names(step_invariant_arg, step_query_names);
+    if (!step_query_names.empty()) {
+      std::string local = make_local(text);
+      for (size_t k = 0; k < step_query_names.size(); k++) {
+        bool known = false;
+        for (const std::string& n : step_names) known = known || n == step_query_names[k];
+        if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", steps_file.c_str(), step_query_names[k].c_str()); return 2; }
+        local += "\nQuery" + std::to_string(k) + " == " + (k < n_step_reach ? "" : "~") + step_query_names[k];
+      }
+      if (vsrmc_step_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+    }
+  }
   if (!reach_arg.empty() || !invariant_arg.empty() || where_report) {
     if (predicates_file.empty()) { std::fprintf(stderr, "Error: -reach / -invariant / -whereReport need -predicates FILE\n"); return 2; }
     std::ifstream pf(predicates_file, std::ios::binary);
@@ -287,29 +350,11 @@ int main(int argc, char** argv) {
     vsrmc_where_desc wd;
     vsrmc_where_describe(w_all, &wd);
     for (int k = 0; k < wd.n_names; k++) where_names.push_back(wd.names[k]);
-    auto split = [&](const std::string& arg) {
-      std::stringstream ss(arg);
-      std::string name;
-      while (std::getline(ss, name, ','))
-        if (!name.empty()) query_names.push_back(name);
-    };
-    split(reach_arg);
+    split_names(reach_arg, query_names);
     n_reach = query_names.size();
-    split(invariant_arg);
+    split_names(invariant_arg, query_names);
     if (!query_names.empty()) {
-      std::string local;                                          // every `Name ==` that is not LOCAL already gets the word in front
-      for (size_t i = 0; i < text.size(); i++) {
-        if (text.compare(i, 2, "==") == 0 && (i == 0 || text[i - 1] != '=') && (i + 2 >= text.size() || text[i + 2] != '=')) {
-          size_t e = local.size();
-          while (e > 0 && std::isspace((unsigned char)local[e - 1])) e--;
-          size_t b = e;
-          while (b > 0 && (std::isalnum((unsigned char)local[b - 1]) || local[b - 1] == '_')) b--;
-          size_t q = b;
-          while (q > 0 && std::isspace((unsigned char)local[q - 1])) q--;
-          if (b < e && !(q >= 5 && local.compare(q - 5, 5, "LOCAL") == 0)) local.insert(b, "LOCAL ");
-        }
-        local.push_back(text[i]);
-      }
+      std::string local = make_local(text);
       for (size_t k = 0; k < query_names.size(); k++) {
         bool known = false;
         for (const std::string& n : where_names) known = known || n == query_names[k];
@@ -452,15 +497,67 @@ int main(int argc, char** argv) {
     }
     return 0;
   };
-  // Init .. the level-`level` state `fp`, printed the way a violation is; `stutter`: a last line "State k+1: Stuttering"
+  // step predicates: every transition out of the newest stored level, where the state predicates scan it
+  struct StepRow { int level; unsigned long long n_states, n_pairs, n_err; unsigned long long count[8]; };
+  std::vector<StepRow> step_rows;
+  vsrmc_step_info si_all, si_query;
+  std::memset(&si_all, 0, sizeof(si_all));
+  std::memset(&si_query, 0, sizeof(si_query));
+  int step_last = 0, step_hit = -1;
+  unsigned long long step_unexamined = 0;
+  bool step_scanned_this_step = false;
+  auto step_newest = [&]() -> int {
+    step_scanned_this_step = false;
+    vsrmc_level_info st;
+    if (vsrmc_checker_status(c, &st) != 0) return -1;
+    if (st.reserved0 != 0 || st.level == step_last || st.n_new == 0) return 0;
+    int32_t r = 0;
+    if (s_all && step_report && (r = vsrmc_checker_step_scan(c, s_all, &si_all)) != 0) return r == VSRMC_E_STATE ? 0 : r;
+    if (s_query && (r = vsrmc_checker_step_scan(c, s_query, &si_query)) != 0) return r == VSRMC_E_STATE ? 0 : r;   // (last: vsrmc_checker_step_successor follows it)
+    step_last = st.level;
+    step_scanned_this_step = true;
+    if (step_report) {
+      StepRow row{si_all.level, (unsigned long long)si_all.n_states, (unsigned long long)si_all.n_pairs, (unsigned long long)si_all.n_err, {0}};
+      for (size_t k = 0; k < step_names.size(); k++) row.count[k] = (unsigned long long)si_all.count[k];
+      step_rows.push_back(row);
+    }
+    if (s_query) {                                                // an action property's violation is reported before a reachability hit of the same level
+      for (size_t k = n_step_reach; k < step_query_names.size() && step_hit < 0; k++)
+        if (si_query.count[k]) step_hit = (int)k;
+      for (size_t k = 0; k < n_step_reach && step_hit < 0; k++)
+        if (si_query.count[k]) step_hit = (int)k;
+    }
+    return 0;
+  };
+  auto step_json_of = [&]() {
+    std::string j = "\"steps\": {\"pairs\": " + std::to_string((unsigned long long)si_all.n_pairs) + ", \"errors\": " + std::to_string((unsigned long long)si_all.n_err) +
+                    ", \"count\": {";
+    for (size_t k = 0; k < step_names.size(); k++) j += (k ? ", \"" : "\"") + step_names[k] + "\": " + std::to_string((unsigned long long)si_all.count[k]);
+    return j + "}}";
+  };
+  // Init .. the level-`level` state `fp`, printed the way a violation is; `stutter`: a last line "State k+1: Stuttering"; step_index / step_ordinal: one
+  // more state, the successor that instance of that state leads to (the pair a step predicate stopped at)
   const char* behaviour_header = "Error: The behavior up to this point is:";
-  auto print_behaviour_to = [&](int level, uint64_t fp, bool stutter) -> bool {
-    uint64_t cap_w = ((uint64_t)level + 2) * (uint64_t)lay.max_record_words, n_states = 0;
-    std::vector<uint64_t> words(cap_w), off((size_t)level + 2);
-    std::vector<int32_t> acts((size_t)level + 2);
-    if (vsrmc_checker_trace_fp(c, level, fp, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states) != 0) {
+  auto print_behaviour_to = [&](int level, uint64_t fp, bool stutter, bool with_step = false, uint64_t step_index = 0, uint32_t step_ordinal = 0) -> bool {
+    uint64_t cap_w = ((uint64_t)level + 3) * (uint64_t)lay.max_record_words, n_states = 0;
+    std::vector<uint64_t> words(cap_w), off((size_t)level + 3);
+    std::vector<int32_t> acts((size_t)level + 3);
+    if (vsrmc_checker_trace_fp(c, level, fp, words.data(), cap_w, off.data(), acts.data(), off.size() - 1, &n_states) != 0) {
       std::printf("Error: %s\n", vsrmc_last_error());
       return false;
+    }
+    if (with_step) {
+      uint64_t len = 0;
+      int32_t act = 0;
+      if (n_states == 0 ||
+          vsrmc_checker_step_successor(c, step_index, step_ordinal, &words[off[n_states - 1]], off[n_states] - off[n_states - 1], &words[off[n_states]],
+                                       cap_w - off[n_states], &len, &act) != 0) {
+        std::printf("Error: %s\n", vsrmc_last_error());
+        return false;
+      }
+      acts[n_states] = act;
+      off[n_states + 1] = off[n_states] + len;
+      n_states++;
     }
     std::printf("%s\n", behaviour_header);
     for (uint64_t t = 0; t < n_states; t++) {
@@ -528,6 +625,11 @@ int main(int argc, char** argv) {
       if (rc != 0) break;
       if (where_hit >= 0) break;
     }
+    if (s_all) {
+      rc = step_newest();
+      if (rc != 0) break;
+      if (step_hit >= 0) break;
+    }
     rc = vsrmc_checker_advance(c, &info, &probed, &what);
     if (rc != 0) break;
     if (what == 3) {                                              // no new level: the deep search was re-based (the levels shrink again)
@@ -544,6 +646,7 @@ int main(int argc, char** argv) {
       rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
       if (terminal_report && !scanned_this_step) { unlisted_levels++; unlisted_deadlocks += (unsigned long long)info.deadlocks; }   // the level this pass expanded has no records
       if (w_all) where_unexamined++;                              // the level this pass inserted is never stored
+      if (s_all) step_unexamined++;
       if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -582,6 +685,7 @@ int main(int argc, char** argv) {
         where_json += (k ? ", \"" : "\"") + where_names[k] + "\": " + std::to_string((unsigned long long)wi_all.count[k]);
       where_json += "}";
     }
+    if (json && step_report && step_scanned_this_step) where_json += ", " + step_json_of();
     if (json && scanned_this_step)                                // (terminal / unsettled: of the level this step expanded, like deadlocks)
       std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu%s, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -606,6 +710,11 @@ int main(int argc, char** argv) {
   // the report covers the newest stored level too when the loop ended before expanding it (-maxDepth, a violation, a full seen-set); an exhausted search's
   // last level is empty and a level already scanned is not scanned again (scan_newest)
   if (terminal_report && rc == 0 && !deadlocked) rc = scan_newest();
+  if (s_all && rc == 0 && step_hit < 0 && where_hit < 0 && !deadlocked && !violated && !probed_violation) {
+    rc = step_newest();
+    if (json && step_report && step_scanned_this_step && rc == 0)       // the newest level was not expanded: a line of its own
+      std::printf("{\"level\": %d, \"expanded\": false, %s}\n", si_all.level, step_json_of().c_str());
+  }
   if (w_all && rc == 0 && where_hit < 0 && !deadlocked) {
     rc = where_newest();
     if (json && where_report && where_scanned_this_step && rc == 0) {   // the newest level was not expanded: a line of its own
@@ -656,6 +765,22 @@ int main(int argc, char** argv) {
                 (unsigned long long)wi_query.count[where_hit], (unsigned long long)wi_query.n_states);
     behaviour_header = "The behavior up to this point is:";
     exit_code = print_behaviour_to(wi_query.level, wi_query.min_fp[where_hit], false) ? 0 : 1;
+  } else if (step_hit >= 0) {
+    const bool inv = step_hit >= (int)n_step_reach;
+    const char* name = step_query_names[step_hit].c_str();
+    if (inv) std::printf("Error: Action property %s is violated.\n", name);
+    else {
+      std::printf("Step satisfying %s found at depth %d (%llu of the level's %llu transitions satisfy it).\n", name, si_query.level,
+                  (unsigned long long)si_query.count[step_hit], (unsigned long long)si_query.n_pairs);
+      behaviour_header = "The behavior up to this point is:";
+    }
+    if (json)
+      std::printf("{\"%s\": \"%s\", \"level\": %d, \"parent_fp\": \"%016llx\", \"ordinal\": %u, \"action\": \"%s\", \"pairs\": %llu}\n", inv ? "action_property_violated" : "step_reached",
+                  name, si_query.level, (unsigned long long)si_query.min_fp[step_hit], si_query.min_ordinal[step_hit], vsrmc_action_name(si_query.min_action[step_hit]),
+                  (unsigned long long)si_query.count[step_hit]);
+    const bool ok = print_behaviour_to(si_query.level, si_query.min_fp[step_hit], false, true, si_query.min_index[step_hit], si_query.min_ordinal[step_hit]);
+    if (ok) std::printf("The last step is %s of State %d.\n", vsrmc_action_name(si_query.min_action[step_hit]), si_query.level);
+    exit_code = ok ? (inv ? 12 : 0) : 1;
   } else if (deadlocked && scanned_this_step && ti.n_terminal) {  // found by the scan, before the level was expanded: there is a behaviour to show
     std::printf("Error: Deadlock reached (%llu state(s) of level %d have no successor).\n", (unsigned long long)ti.n_terminal, ti.level);
     exit_code = print_behaviour_to(ti.level, ti.min_fp, false) ? 11 : 1;
@@ -699,6 +824,36 @@ int main(int argc, char** argv) {
                   where_unexamined ? "levels that were examined" : info.n_new == 0 && !incomplete ? "state space" : "levels searched");
     if (where_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.\n", where_unexamined);
     exit_code = exit_code ? exit_code : 14;
+  }
+  if (n_step_reach && rc == 0 && step_hit < 0 && where_hit < 0 && !violated && !probed_violation && !deadlocked) {
+    for (size_t k = 0; k < n_step_reach; k++)
+      std::printf("No step satisfying %s was found in the %s.\n", step_query_names[k].c_str(),
+                  step_unexamined ? "levels that were examined" : info.n_new == 0 && !incomplete ? "state space" : "levels searched");
+    if (step_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.\n", step_unexamined);
+    exit_code = exit_code ? exit_code : 14;
+  }
+  if (step_report && rc == 0) {
+    unsigned long long pairs = 0, errs = 0;
+    for (const StepRow& r : step_rows) { pairs += r.n_pairs; errs += r.n_err; }
+    if (!json)
+      for (const StepRow& r : step_rows) {
+        std::printf("Step report: level %d: %llu pairs from %llu states, %llu errors", r.level, r.n_pairs, r.n_states, r.n_err);
+        for (size_t k = 0; k < step_names.size(); k++) std::printf(", %s %llu", step_names[k].c_str(), r.count[k]);
+        std::printf("\n");
+      }
+    for (size_t k = 0; k < step_names.size(); k++) {
+      unsigned long long total = 0;
+      size_t with = 0;
+      for (const StepRow& r : step_rows) { total += r.count[k]; with += r.count[k] ? 1 : 0; }
+      std::printf("Step report: %s holds on %llu of %llu pairs, in %zu of %zu examined levels", step_names[k].c_str(), total, pairs, with, step_rows.size());
+      bool first = true;
+      for (const StepRow& r : step_rows)
+        if (r.count[k] != r.n_pairs) { std::printf("%slevel %d: false on %llu", first ? " (" : ", ", r.level, r.n_pairs - r.count[k]); first = false; }
+      std::printf("%s.\n", first ? "" : ")");
+    }
+    std::printf("Step report: %llu instances raise an evaluation error (not evaluated).\n", errs);
+    if (step_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.  Probed levels are not examined either.\n", step_unexamined);
+    if (probe2_at > 0 || probe3_at > 0) std::printf("The levels of -probe2At / -probe3At were not examined: they have no records.\n");
   }
   if (where_report && rc == 0) {
     for (size_t k = 0; k < where_names.size(); k++) {
@@ -769,6 +924,8 @@ int main(int argc, char** argv) {
   if (c) vsrmc_checker_destroy(c);
   if (w_all) vsrmc_where_destroy(w_all);
   if (w_query) vsrmc_where_destroy(w_query);
+  if (s_all) vsrmc_where_destroy(s_all);
+  if (s_query) vsrmc_where_destroy(s_query);
   vsrmc_model_destroy(m);
   return exit_code;
 }
