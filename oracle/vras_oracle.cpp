@@ -531,23 +531,30 @@ int check_invariants(const Params& P, const State& s) {
     if ((P.invariant_mask & 1) && holders == 0) bad |= 1;                                            // AcknowledgedWriteNotLost :877-882
     if ((P.invariant_mask & 2) && !(holders >= P.R / 2 + 1)) bad |= 2;                               // AcknowledgedWritesExistOnMajority :865-871
   }
-  if (P.invariant_mask & (4 | 16)) {
-    for (int opn = 1; opn <= P.n; opn++)
-      for (int r1 = 1; r1 <= P.R; r1++)
-        for (int r2 = 1; r2 <= P.R; r2++) {
-          if (!(opn <= s.rep[r1].commit && opn <= s.rep[r2].commit)) continue;                       // :843-844 / :855-856
+  // The two divergence invariants are \A op_number : ~\E r1, r2 : ...: TLC leaves the \A at the first op_number that fails and the \E at
+  // the first pair that satisfies it, so an entry outside a log is an evaluation error only if it is read before a divergence is found
+  // (op_number ascending, then r1, then r2; the conjuncts of :855-858 in their order).
+  if (P.invariant_mask & 4) {                                                                        // NoLogDivergence :840-845
+    for (int opn = 1; opn <= P.n && !(bad & 4); opn++)
+      for (int r1 = 1; r1 <= P.R && !(bad & 4); r1++)
+        for (int r2 = 1; r2 <= P.R && !(bad & 4); r2++) {
+          if (!(opn <= s.rep[r1].commit && opn <= s.rep[r2].commit)) continue;                       // :843-844
           const Log &a = s.rep[r1].log, &b = s.rep[r2].log;
-          if (P.invariant_mask & 4) {                                                                // NoLogDivergence :840-845
-            if (opn > a.hi || opn > b.hi) throw EvalError("rep_log[r][op_number] outside the log (NoLogDivergence, VRAS.tla:845)");
-            if (a.v[opn] != b.v[opn]) bad |= 4;
-          }
-          if (P.invariant_mask & 16) {                                                               // NoAppStateDivergence :852-858
-            const std::vector<int>&x = s.rep[r1].app_state, &y = s.rep[r2].app_state;
-            if (opn > (int)x.size() || opn > (int)y.size()) throw EvalError("rep_app_state[r][op_number] outside the sequence (NoAppStateDivergence, VRAS.tla:857)");
-            if (x[opn - 1] != y[opn - 1]) {                                                          // :857
-              if (opn > a.hi) throw EvalError("rep_log[r1][op_number] outside the log (NoAppStateDivergence, VRAS.tla:858)");
-              if (a.v[opn] == x[opn - 1]) bad |= 16;                                                 // :858
-            }
+          if (opn > a.hi || opn > b.hi) throw EvalError("rep_log[r][op_number] outside the log (NoLogDivergence, VRAS.tla:845)");
+          if (a.v[opn] != b.v[opn]) bad |= 4;
+        }
+  }
+  if (P.invariant_mask & 16) {                                                                       // NoAppStateDivergence :852-858
+    for (int opn = 1; opn <= P.n && !(bad & 16); opn++)
+      for (int r1 = 1; r1 <= P.R && !(bad & 16); r1++)
+        for (int r2 = 1; r2 <= P.R && !(bad & 16); r2++) {
+          if (!(opn <= s.rep[r1].commit && opn <= s.rep[r2].commit)) continue;                       // :855-856
+          const Log& a = s.rep[r1].log;
+          const std::vector<int>&x = s.rep[r1].app_state, &y = s.rep[r2].app_state;
+          if (opn > (int)x.size() || opn > (int)y.size()) throw EvalError("rep_app_state[r][op_number] outside the sequence (NoAppStateDivergence, VRAS.tla:857)");
+          if (x[opn - 1] != y[opn - 1]) {                                                            // :857
+            if (opn > a.hi) throw EvalError("rep_log[r1][op_number] outside the log (NoAppStateDivergence, VRAS.tla:858)");
+            if (a.v[opn] == x[opn - 1]) bad |= 16;                                                   // :858
           }
         }
   }

@@ -488,10 +488,12 @@ int check_invariants(const Params& P, const State& s) {
     if ((P.invariant_mask & 1) && holders == 0) bad |= 1;                                            // AcknowledgedWriteNotLost :830-835
     if ((P.invariant_mask & 2) && !(holders >= P.R / 2 + 1)) bad |= 2;                               // AcknowledgedWritesExistOnMajority :818-824
   }
+  // \A op_number : ~\E r1, r2 : ...: TLC leaves the \A at the first op_number that fails and the \E at the first pair that satisfies it, so
+  // an entry outside a log is an evaluation error only if it is read before a divergence is found (op_number ascending, then r1, then r2)
   if (P.invariant_mask & 4) {                                                                        // NoLogDivergence :806-811
-    for (int opn = 1; opn <= P.n; opn++)
-      for (int r1 = 1; r1 <= P.R; r1++)
-        for (int r2 = 1; r2 <= P.R; r2++) {
+    for (int opn = 1; opn <= P.n && !(bad & 4); opn++)
+      for (int r1 = 1; r1 <= P.R && !(bad & 4); r1++)
+        for (int r2 = 1; r2 <= P.R && !(bad & 4); r2++) {
           if (!(opn <= s.rep[r1].commit && opn <= s.rep[r2].commit)) continue;
           const Log &a = s.rep[r1].log, &b = s.rep[r2].log;
           if (opn > a.hi || opn > b.hi) throw EvalError("rep_log[r][op_number] outside the log (NoLogDivergence, VRST.tla:811)");

@@ -43,10 +43,14 @@ def _pow2_at_least(x):
 
 
 class Case:
-    """the oracle's side of one seed set under one invariant mask"""
+    """the oracle's side of one seed set under one invariant mask.  `orc` is the oracle module of the model: oracle/orc.py with key = (R, C, n, L),
+    or oracle/orc2.py / orc3.py with key = (R, n, L) — then `make_model(vt, inv_mask)` builds the product's model of the same constants (no SYMMETRY: one
+    view hash per record) and `verdict(words, inv_mask)` gives the oracle's verdict on a record where orc.invariants alone does not (an evaluation error
+    that the kernels report as a violation)."""
 
-    def __init__(self, orc, key, recs, succ, inv_mask=1):
+    def __init__(self, orc, key, recs, succ, inv_mask=1, make_model=None, verdict=None):
         self.orc, self.key, self.recs, self.succ = orc, key, recs, succ
+        self.inv_mask, self.make_model, self.verdict = inv_mask, make_model, verdict
         self.P = orc.Params(*key, invariant_mask=inv_mask)
         self.fps = [orc.fingerprint(self.P, r)[0] for r in recs]
         assert len(set(self.fps)) == len(recs), "the seeds are distinct states"
@@ -68,18 +72,21 @@ class Case:
                 if s["fp"] in seed_fp:
                     continue
                 self.by_fp[s["fp"]].append((s["auxkey"], i, s))
-                inv = s["inv"] if inv_mask == 1 else orc.invariants(self.P, s["words"])
+                inv = self.verdict_of(s["words"]) if (verdict or inv_mask != 1) else s["inv"]
                 if inv:
                     self.viol[s["fp"]] = self.viol.get(s["fp"], 0) | inv
         self.new = sorted(self.by_fp)
         self.ties = [f for f, v in self.by_fp.items() if len(set(ak for ak, _i, _s in v)) > 1]
         self.new_words_dev = 0                                      # words of the new level in device layout (wire + one view hash per permutation)
         perms = 1
-        for k in range(2, key[2] + 1):
+        for k in range(2, (1 if make_model else key[2]) + 1):
             perms *= k
         for f in self.new:
             self.new_words_dev += len(self.by_fp[f][0][2]["words"]) + perms
         self.seed_words_dev = sum(len(r) + perms for r in recs)
+
+    def verdict_of(self, words):
+        return self.verdict(words, self.inv_mask) if self.verdict else self.orc.invariants(self.P, words)
 
     def tie_producers(self):
         return sorted(set(i for f in self.ties for _ak, i, _s in self.by_fp[f]))
@@ -92,8 +99,11 @@ class Case:
 
 
 def make_checker(vt, case, exact, frontier_words=None):
-    R, C_, n, L = case.key
-    m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L, invariant_mask=int(case.P.arr[7]))
+    if case.make_model:
+        m = case.make_model(vt, int(case.P.arr[7]))
+    else:
+        R, C_, n, L = case.key
+        m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L, invariant_mask=int(case.P.arr[7]))
     fw = frontier_words or _pow2_at_least(max(1 << 24, 2 * max(case.new_words_dev, case.seed_words_dev)))
     fs = _pow2_at_least(max(1 << 16, 4 * max(len(case.new), len(case.recs))))
     mc = vt.ModelChecker(m, table_log2=23, frontier_words=fw, frontier_states=fs, pending_entries=1 << 22 if exact else 1 << 16,
@@ -139,7 +149,7 @@ def check_level(vt, case, mc, d, label, n_traces=48):
         assert (d["viol_fp"], d["viol_mask"]) == (vfp, vmask), (label, d["viol_fp"], d["viol_mask"], vfp, vmask)
         idx = d["viol_index"]
         t = mc.trace(2, idx)
-        assert case.orc.fingerprint(case.P, t[-1][1])[0] == vfp and case.orc.invariants(case.P, t[-1][1]) != 0
+        assert case.orc.fingerprint(case.P, t[-1][1])[0] == vfp and case.verdict_of(t[-1][1]) != 0
     else:
         assert d["viol_mask"] == 0 and d["viol_fp"] == M64, (label, d["viol_fp"], d["viol_mask"])
     # traces: [the seed the meta word names, the state]
@@ -158,8 +168,8 @@ def check_level(vt, case, mc, d, label, n_traces=48):
     return len(sample)
 
 
-def run_step(vt, orc, key, recs, succ, exact, inv_mask=1, label=""):
-    case = Case(orc, key, recs, succ, inv_mask)
+def run_step(vt, orc, key, recs, succ, exact, inv_mask=1, label="", **model_kw):
+    case = Case(orc, key, recs, succ, inv_mask, **model_kw)
     m, mc = make_checker(vt, case, exact)
     try:
         mc.seed_records(*case.batch())
@@ -175,9 +185,9 @@ def run_step(vt, orc, key, recs, succ, exact, inv_mask=1, label=""):
                 act_generated=case.act, traces=n_tr, step_seconds=dt, expand_ms=d["expand_ms"])
 
 
-def parts_without_ties(orc, key, recs, succ):
+def parts_without_ties(orc, key, recs, succ, **model_kw):
     """the seed set as parts a single-pass level can take -> ([part: list of seed numbers], seeds left out)"""
-    whole = Case(orc, key, recs, succ)
+    whole = Case(orc, key, recs, succ, **model_kw)
     if not whole.ties:
         return [list(range(len(recs)))], 0
     groups = collections.defaultdict(list)
@@ -186,7 +196,7 @@ def parts_without_ties(orc, key, recs, succ):
     parts, left = [], 0
     for g in sorted(groups):
         idx = groups[g]
-        c = Case(orc, key, [recs[i] for i in idx], [succ[i] for i in idx])
+        c = Case(orc, key, [recs[i] for i in idx], [succ[i] for i in idx], **model_kw)
         drop = set(c.tie_producers())
         left += len(drop)
         parts.append([i for k, i in enumerate(idx) if k not in drop])

@@ -405,7 +405,10 @@ VSR_HD void hash_child(const Model& M, PTR rec, const Delta& D, u64* Hc) {
 // Invariants on the child (VRAS.tla:840-894): mask of VIOLATED ones.  bit0 AcknowledgedWriteNotLost, bit1
 // AcknowledgedWritesExistOnMajority, bit2 NoLogDivergence, bit3 CommitNumberNeverHigherThanOpNumber, bit4 NoAppStateDivergence.
 // NoLogDivergence / NoAppStateDivergence read rep_log[r][op] for op <= commit: beyond the log that is a TLC evaluation error; it is
-// reported as a violation of the bit here (MaybeExecuteOps has raised the evaluation error in the action already).
+// reported as a violation of the bit here (MaybeExecuteOps has raised the evaluation error in the action already).  The quantifiers run
+// over all pairs, r1 = r2 included: on the diagonal nothing can differ, but a single replica with commit > Len(log) reads outside its log
+// there under NoLogDivergence, which is the per-replica term below (the pair loop stays r1 != r2; :857 is false on the diagonal before
+// :858 reads the log).
 template <typename PTR>
 VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
   int bad = 0;
@@ -431,7 +434,11 @@ VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
       if ((M.inv_mask & 2) && !(holders >= M.R / 2 + 1)) bad |= 2;   // :865-871
     }
   if (M.inv_mask & (4 | 16))
-    for (int opn = 1; opn <= M.n; opn++)
+    for (int opn = 1; opn <= M.n; opn++) {
+      if (M.inv_mask & 4)
+#pragma unroll
+        for (int r = 1; r <= 3; r++)                             // NoLogDivergence at r1 = r2 = r: the entry must exist
+          if (r <= M.R && opn <= a_commit(Aw[r]) && !(blog_entry(b_log(Aw[r]), opn) & 1)) bad |= 4;
 #pragma unroll
       for (int r1 = 1; r1 <= 3; r1++)
 #pragma unroll
@@ -444,6 +451,7 @@ VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
               (!(e1 & 1) || (e1 >> 1) == c_app(Aw[r1], opn)))                      //                       :858
             bad |= 16;
         }
+    }
   if (M.inv_mask & 8)                                            // CommitNumberNeverHigherThanOpNumber :892-894
 #pragma unroll
     for (int r = 1; r <= 3; r++)

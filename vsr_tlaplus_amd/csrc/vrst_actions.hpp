@@ -411,7 +411,8 @@ VSR_HD void hash_child(const Model& M, PTR rec, const Delta& D, u64* Hc) {
 // Invariants on the child (VRST.tla:806-847): mask of VIOLATED ones.  bit0 AcknowledgedWriteNotLost, bit1
 // AcknowledgedWritesExistOnMajority, bit2 NoLogDivergence, bit3 CommitNumberNeverHigherThanOpNumber.  NoLogDivergence reads
 // rep_log[r][op] for op <= commit: beyond the log that is a TLC evaluation error; it is reported as a violation of bit2 here
-// (bit3 fails in the same state).
+// (bit3 fails in the same state).  The quantifier runs over all pairs, r1 = r2 included: on the diagonal nothing can differ, but a single
+// replica with commit > Len(log) reads outside its log there, which is the per-replica term below (the pair loop stays r1 < r2).
 template <typename PTR>
 VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
   int bad = 0;
@@ -437,7 +438,10 @@ VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
       if ((M.inv_mask & 2) && !(holders >= M.R / 2 + 1)) bad |= 2;   // :818-824
     }
   if (M.inv_mask & 4)                                            // NoLogDivergence :806-811
-    for (int opn = 1; opn <= M.n; opn++)
+    for (int opn = 1; opn <= M.n; opn++) {
+#pragma unroll
+      for (int r = 1; r <= 5; r++)                               // r1 = r2 = r: the entry must exist
+        if (r <= M.R && opn <= a_commit(Aw[r]) && !(blog_entry(b_log(Aw[r]), opn) & 1)) bad |= 4;
 #pragma unroll
       for (int r1 = 1; r1 <= 5; r1++)
 #pragma unroll
@@ -447,6 +451,7 @@ VSR_HD int check_invariants_child(const Model& M, PTR rec, const Delta& D) {
           const int e1 = blog_entry(b_log(Aw[r1]), opn), e2 = blog_entry(b_log(Aw[r2]), opn);
           if (!(e1 & 1) || !(e2 & 1) || e1 != e2) bad |= 4;
         }
+    }
   if (M.inv_mask & 8)                                            // CommitNumberNeverHigherThanOpNumber :845-847
 #pragma unroll
     for (int r = 1; r <= 5; r++)
