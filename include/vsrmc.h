@@ -288,13 +288,19 @@ typedef struct vsrmc_terminal_info {
 int32_t vsrmc_checker_terminal_scan(vsrmc_checker* c, vsrmc_terminal_info* out);
 int32_t vsrmc_checker_terminal_states(vsrmc_checker* c, uint64_t* fps, uint8_t* flags, uint64_t cap, uint64_t* n);
 
-/* ---- state predicates: user-written invariants and reachability queries (VSR.tla only) -----------------------------------------
+/* ---- state predicates: user-written invariants and reachability queries ---------------------------------------------------------
  * A closed expression language over the lowered record, written in TLA+ syntax — the language, what is refused and where an evaluation
  * departs from TLC (accesses outside a domain have a defined result; model-value literals are refused under SYMMETRY; the aux variables are seen
  * through the representative the search keeps) are specified in csrc/vsr_where_parse.hpp.  The text holds one expression or definitions
  * `Name == expr`; every definition not written `LOCAL Name == expr` is exported, at most 8; exported predicate k is bit k everywhere below.
  * vsrmc_where_compile: needs no device.  VSRMC_E_ARG with "line:col: reason" in vsrmc_last_error() for a text that is refused (models 2 and 3:
  *   "state predicates: VSR.tla only"), VSRMC_E_REP for a program beyond 4096 ops or an operand depth beyond 32.
+ * vsrmc_predicates_compile: the model-generic entry.  For a VSR.tla model it returns exactly what vsrmc_where_compile returns, op for op; for a model
+ *   of vsrmc_model2_from_constants / vsrmc_model3_from_constants (or their cfgs) it compiles the same language over that spec's variables
+ *   (no_progress, AnyDest, StateTransfer, m.log; on VR_APP_STATE.tla also rep_app_state and rep_recv_dvc — csrc/vsr_where_parse.hpp).  The object goes
+ *   through every call below unchanged; a program is refused (VSRMC_E_ARG, "state predicates: compiled for another model") by any model but the
+ *   one it was compiled for — the two analysis models with equal constants are different models.  vsrmc_where_compile and vsrmc_step_compile keep
+ *   refusing the analysis models.
  * vsrmc_where_batch: n wire records of the caller (the layout of vsrmc_terminal_batch); flags[i] = the bits of record i.
  * vsrmc_checker_where_scan: k_where (csrc/vsr_where.hpp) over the newest STORED level.  Valid exactly where vsrmc_checker_terminal_scan is
  *   (VSRMC_E_STATE on a sharded checker, on seen-set-only levels, after a failed search), any number of times; changes nothing a later call
@@ -321,6 +327,7 @@ typedef struct vsrmc_where_info {
   double kernel_ms;                                /* HIP-event time of k_where */
 } vsrmc_where_info;
 int32_t vsrmc_where_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
+int32_t vsrmc_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
 void vsrmc_where_destroy(vsrmc_where* w);
 int32_t vsrmc_where_describe(const vsrmc_where* w, vsrmc_where_desc* out);
 int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint8_t* flags);

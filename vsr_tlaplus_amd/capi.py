@@ -136,6 +136,7 @@ SYMBOLS = {
     "vsrmc_checker_terminal_scan": (C.c_int32, [V, C.POINTER(TerminalInfo)]),
     "vsrmc_checker_terminal_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_where_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
+    "vsrmc_predicates_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_where_destroy": (None, [V]),
     "vsrmc_where_describe": (C.c_int32, [V, C.POINTER(WhereDesc)]),
     "vsrmc_where_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V]),

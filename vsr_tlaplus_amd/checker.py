@@ -170,6 +170,13 @@ class Model:
         check(capi.load().vsrmc_where_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
         return Where(h, self)
 
+    def compile_predicates(self, text):
+        """State predicates for ANY model -> Where.  A VSR.tla model: exactly compile_where's program.  second_model / third_model: the same language
+        over that spec's variables (csrc/vsr_where_parse.hpp).  Needs no device.  Raises VsrmcError with "line:col: reason" for a text that is refused."""
+        h = C.c_void_p()
+        check(capi.load().vsrmc_predicates_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return Where(h, self)
+
     def where_flags(self, w, words, off, device=0):
         """One byte per state of a batch (k_where): bit k = exported predicate k of `w` holds."""
         words = np.ascontiguousarray(words, dtype=np.uint64)

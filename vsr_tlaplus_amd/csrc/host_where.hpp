@@ -1,4 +1,5 @@
-// host_where.hpp — state predicates: the host side of k_where (vsr_where.hpp) — compiling a text (vsr_where_parse.hpp), a caller's batch, the scan of
+// host_where.hpp — state predicates: the host side of k_where (vsr_where.hpp) — compiling a text (vsr_where_parse.hpp; vsrmc_predicates_compile for any model,
+// vsrmc_where_compile for VSR.tla alone), picking the model's instantiation, a caller's batch, the scan of
 // the checker's newest stored level, the list the last scan left (included by vsrmc.hip: one translation unit, the sections share its
 // anonymous-namespace helpers).
 #pragma once
@@ -6,12 +7,13 @@
 struct vsrmc_where {
   WhereProgram prog;
   int R, C, n, L, symmetry;            // the model it was compiled for: the unfolding depends on these
+  int model_id = 0;                    // and the layout the loads address (vsrmc_predicates_compile; the two older entries compile for VSR.tla only)
 };
 
 namespace {
 
 bool where_fits(const vsrmc_where* w, const Model& M, int symmetry) {
-  return M.model_id == 0 && w->R == M.R && w->C == M.C && w->n == M.n && w->L == M.L && w->symmetry == symmetry;
+  return w->model_id == M.model_id && w->R == M.R && w->C == M.C && w->n == M.n && w->L == M.L && w->symmetry == symmetry;
 }
 
 // one launch over n refs; the program is uploaded and the WhereCtl at d_ctl initialised here (d_prog: room for WHERE_MAX_OPS ops); e0 / e1, when given,
@@ -26,7 +28,8 @@ int launch_where(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t 
   HIPCHK(hipStreamSynchronize(stream));                            // (both sources are pageable host memory that the caller may free)
   const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)num_cus * 8));
   if (e0) HIPCHK(hipEventRecord(e0, stream));
-  hipLaunchKernelGGL(k_where, dim3(grid), dim3(256), 0, stream, M, (const u32*)d_prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list,
+  auto* const kernel = M.model_id == 1 ? k_where<1> : M.model_id == 2 ? k_where<2> : k_where<0>;   // (where_fits: the program is this model's)
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, M, (const u32*)d_prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list,
                      list_cap);
   HIPCHK(hipGetLastError());
   if (e1) HIPCHK(hipEventRecord(e1, stream));
@@ -49,6 +52,23 @@ int32_t vsrmc_where_compile(const vsrmc_model* m, const char* text, vsrmc_where*
     return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
   }
   w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry;
+  *out = w;
+  return 0;
+}
+
+// the model-generic entry: VSR.tla -> what vsrmc_where_compile gives, op for op; the analysis models -> their own variable table (vsr_where_parse.hpp)
+int32_t vsrmc_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out) {
+  if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
+  if (m->M.model_id == 0) return vsrmc_where_compile(m, text, out);
+  *out = nullptr;
+  vsrmc_where* w = new vsrmc_where();
+  std::string err;
+  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err);
+  if (rc) {
+    delete w;
+    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
+  }
+  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry; w->model_id = m->M.model_id;
   *out = w;
   return 0;
 }

@@ -12,6 +12,10 @@
 // Output per exported predicate k < 8: bit k of an optional flag byte per record, an exact counter (wave ballots summed in scalar registers, one atomic
 // per wave at the end), the smallest fingerprint that satisfies it (wave reduction, one atomicMin per wave with a hit) and, for records with any bit
 // set, a (fingerprint, index, bits) triple appended wave-wise to a list of which the first list_cap that arrive are kept (WhereCtl::n_list = true number).
+//
+// One instantiation per model, as k_terminal<MODEL>: k_where<0> is VSR.tla's and compiles exactly what it compiled before; k_where<1> (VR_STATE_TRANSFER.tla)
+// and k_where<2> (VR_APP_STATE.tla) add five ops for what those records store differently — an entry normalised from either encoding, the 9-bit log's length,
+// m.log with its first_op domain, an application-state entry — behind `if constexpr (MODEL != 0)`.  The slots of the held DoViewChanges are plain W_LDBITS.
 #pragma once
 #include "vsr_model.hpp"
 
@@ -34,6 +38,14 @@ enum {
   W_MEND,      // arg: loop | forall << 1 | pc of the first body op << 2 | primed << 14
   W_OUT,       // arg: k : pops a boolean into bit k of the result
   W_STEPACT,   // step programs only (vsr_step.hpp): pushes the action id of the pair
+  // the analysis models (model_id 1, 2: vrst_actions.hpp / vras_actions.hpp), in k_where<1> / k_where<2> only.  A log entry there is [operation |-> v]; every
+  // entry, wherever it is stored, is brought to ONE form before anything looks at it: value index + 1, 0 = absent.
+  W_ENTN,      // arg: 0 the replica-side entry (1 | value << 1, 3 bits) on top, 1 the message-side entry byte (1 | value << 3) on top : -> value + 1, or 0
+  W_BLOGLEN,   // number of entries of the 9-bit log (3 entries x 3 bits) on top
+  W_MLOGENT,   // arg: loop(1) | i(2) << 1, i in 1..3 : m.log[i] normalised — of a DoViewChangeMsg / StartViewMsg the sequence's entry i, of a NewStateMsg the
+               // entry i with first_op <= i <= op_number, 0 for every other type and outside the domain
+  W_MLOGLEN,   // arg: loop : the number of entries m.log holds (the sum of W_MLOGENT != 0 over i)
+  W_APPENT,    // arg: word(8) | i(2) << 8 : rep_app_state[r][i] normalised, read from the A word rec[word]: present iff i <= commit number (model 2)
   W_OPCOUNT
 };
 enum { WHERE_MAX_OPS = 4096, WHERE_MAX_DEPTH = 32, WHERE_MAX_EXPORTS = 8 };
@@ -53,7 +65,16 @@ struct WhereNoPair { static constexpr bool is_pair = false; };
 
 // One record through the program.  `S` is the operand stack (S[slot] -> int&); valid = the lane has a record; wmax = the largest nmsg of the lanes that
 // run together (on the host: nmsg).  Returns the exported bits.
-template <typename STACK, typename PTR, typename PAIR = WhereNoPair>
+// m.log[i] of the bag word w, normalised (W_MLOGENT)
+VSR_HD int where_mlog_entry(u64 w, int i) {
+  const int t = m_type(w);
+  const bool in_dom = t == T_DVC || t == T_SV || (t == T_NEWSTATE && i >= m_first_op(w) && i <= m_op(w));
+  const int b = (int)((m_lg(w) >> (8 * (i - 1))) & 0xFF);
+  return (in_dom && (b & 7)) ? ((b >> 3) & 3) + 1 : 0;
+}
+
+// MODEL: the model id the program was compiled for.  0 (VSR.tla, and every step program) compiles none of the analysis models' ops.
+template <typename STACK, typename PTR, typename PAIR = WhereNoPair, int MODEL = 0>
 VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool valid, int nmsg, int wmax, STACK& S, const PAIR& pair = PAIR()) {
   u32 bits = 0;
   int sp = 0, pc = 0;
@@ -144,6 +165,28 @@ VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool vali
         if constexpr (PAIR::is_pair) {
           if ((op >> 24) == W_STEPACT) { S[sp++] = pair.action; break; }
         }
+        if constexpr (MODEL != 0) {
+          const u32 code = op >> 24;
+          if (code >= (u32)W_ENTN) {
+            if (code == W_ENTN) {
+              const int e = S[sp - 1];
+              S[sp - 1] = (arg & 1) ? ((e & 7) ? ((e >> 3) & 3) + 1 : 0) : ((e & 1) ? ((e >> 1) & 3) + 1 : 0);
+            } else if (code == W_BLOGLEN) {
+              const int lg = S[sp - 1];
+              S[sp - 1] = (lg & 1) + ((lg >> 3) & 1) + ((lg >> 6) & 1);
+            } else if (code == W_MLOGENT) {
+              S[sp++] = where_mlog_entry((arg & 1) ? mw1 : mw0, (int)((arg >> 1) & 3));
+            } else if (code == W_MLOGLEN) {
+              const u64 w = (arg & 1) ? mw1 : mw0;
+              S[sp++] = (where_mlog_entry(w, 1) != 0) + (where_mlog_entry(w, 2) != 0) + (where_mlog_entry(w, 3) != 0);
+            } else {                                                  // W_APPENT
+              const u64 A = valid ? rec[arg & 0xFF] : (u64)0;
+              const int i = (int)((arg >> 8) & 3);
+              S[sp++] = i <= a_commit(A) ? (int)((A >> (34 + 2 * (i - 1))) & 3) + 1 : 0;
+            }
+            break;
+          }
+        }
         const int b = S[--sp], a = S[sp - 1];
         int r = 0;
         switch (op >> 24) {
@@ -183,6 +226,7 @@ struct WhereLdsStack {                // [slot][lane of the block]
   __device__ __forceinline__ int& operator[](int slot) const { return base[slot * 256]; }
 };
 
+template <int MODEL>
 __global__ void __launch_bounds__(256)
 k_where(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restrict__ words, const u64* __restrict__ refs, const u64* __restrict__ fps,
         u64 n, uint8_t* flags, WhereCtl* ctl, u64* list, u64 list_cap) {
@@ -203,7 +247,7 @@ k_where(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restr
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
     wmax = (int)VSR_WHERE_UNI(wmax);
-    const u32 raw = where_run(prog, M.fixed, rec, valid, nmsg, wmax, S);
+    const u32 raw = where_run<WhereLdsStack, const u64*, WhereNoPair, MODEL>(prog, M.fixed, rec, valid, nmsg, wmax, S);
     const u32 bits = valid ? raw : 0;                              // (a lane without a record ran the program over zeros: TRUE would count it)
     if (valid && flags) flags[i] = (uint8_t)bits;
     n_scanned += (u32)__popcll(__ballot(valid));

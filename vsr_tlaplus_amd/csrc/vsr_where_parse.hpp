@@ -38,6 +38,34 @@
 // (rep_status[r] = 1), primes, temporal operators, CHOOSE, LAMBDA, set constructors, a quantifier over any other set, more than 8 exported names.
 // Code 2 = VSRMC_E_REP: a program beyond 4096 ops or an operand depth beyond 32.
 //
+// THE ANALYSIS MODELS (vsrmc_predicates_compile on a model of VR_STATE_TRANSFER.tla, model_id 1, or VR_APP_STATE.tla, model_id 2).  The grammar, precedences,
+// definitions, LOCAL, comments, the caps, the "line:col: reason" refusals and the SYMMETRY rule above carry over; the variable table is the spec's own
+// (what depends on the model is WhereLayout below: VSR.tla's table is the same code with its own row, and compiles to the ops it always did).
+//   integer     ... ReplicaCount StartViewOnTimerLimit NoProgressChangeLimit Cardinality(Values) AnyDest
+//   quantifier  S = replicas | Values | a..b | DOMAIN messages | DOMAIN s for a log s | rep_recv_dvc[r] (VR_APP_STATE.tla); x \in S for all but the last two
+//   state       rep_status[r] (Normal ViewChange StateTransfer) rep_view_number[r] rep_op_number[r] rep_commit_number[r] rep_last_normal_view[r]
+//               rep_sent_dvc[r] rep_sent_sv[r] no_progress[r]   rep_peer_op_number[r][p]   no_progress_ctr aux_svc aux_client_acked[v] v \in DOMAIN aux_client_acked
+//   logs s      rep_log[r];  m.log of a bound message — of a DoViewChangeMsg or StartViewMsg the sequence, of a NewStateMsg the function on
+//               first_op..op_number, of any other type empty;  on VR_APP_STATE.tla also rep_app_state[r] and d.log of a held DoViewChange.
+//               Len(s)   i \in DOMAIN s   \A / \E i \in DOMAIN s   s[i]   s[i].operation.  An entry is [operation |-> v]: s[i] = t[j] and s[i] # t[j] compare
+//               entries wherever they are stored (the replica-side and message-side encodings are brought to one form by an op before anything looks at
+//               them), s[i].operation is a value.  .view_number / .client_id / .request_number of an entry do not exist in these specs and are refused.
+//   messages    as above: m.type .view_number .dest .source .op_number .commit_number .last_normal_vn .first_op, m.message and m.message.operation,
+//               messages[m]; m.dest = AnyDest.  AnyDest equals no replica number; as an index it is out of range.
+//   VR_APP_STATE.tla only   Cardinality(rep_recv_dvc[r]);  \A / \E d \in rep_recv_dvc[r] (unfolded over the source slots, guarded by the present bit: no loop;
+//               r may be any integer expression) with d.type d.view_number d.source d.dest (= r) d.last_normal_vn d.op_number d.commit_number d.log.
+//               On VR_STATE_TRANSFER.tla rep_app_state and rep_recv_dvc are unknown identifiers: there the DoViewChanges a replica has counted are the bag
+//               keys with messages[m] = 0.
+// Refused with a reason that names the model: clients ClientCount rep_client_table rep_svc_recv rep_dvc_recv Recovering; aux_restart rep_rec_number
+// rep_rec_recv (never written under these cfgs: the lowering stores none of them); step_action.  Refused as above: primes, UNCHANGED, temporal operators.  A
+// whole log as a value (m.log = rep_log[r]) is refused: compare lengths and entries.
+// WHERE THIS DEPARTS FROM TLC, beyond the list above (whose conventions hold: an absent entry reads 0 and its operation equals Nil, an absent field reads 0,
+// an index out of range yields -1, \div by zero gives 0):
+//   * Len(m.log) is the number of entries the message carries.  For a NewStateMsg m.log is a function on first_op..op_number, not a sequence, and TLA+ gives
+//     Len of it no meaning.
+//   * AnyDest is an integer here (7: what m.dest reads for such a message; no replica has the number), so m.dest < AnyDest is TRUE for an addressed message
+//     where TLC would refuse to compare a model value with an integer.
+//
 // STEP PREDICATES (where_compile(.., step = true); vsrmc_step_compile): predicates over a state and its successor — the safety half of PROPERTY, an action
 // property [][P]_vars — evaluated on every transition the checker generates (vsr_step.hpp).  The same grammar plus:
 //   prime        ' after a state variable name (rep_view_number'[r], rep_log'[r][i].operation, messages', aux_svc') and after a primary expression
@@ -309,8 +337,27 @@ struct Parser {
   }
 };
 
-struct Binding { std::string name; int kind; int v; bool primed = false; };   // kind 0: integer constant, 1: value constant (index + 1), 2: message loop v (primed: over messages')
+// kind 0: integer constant, 1: value constant (index + 1), 2: message loop v (primed: over messages'), 3: a held DoViewChange, v = replica << 4 | source slot
+struct Binding { std::string name; int kind; int v; bool primed = false; };
 struct Def { NodeP body; };
+
+// What depends on the model: where a variable lies in the record and which names exist (vsr_model.hpp, vrst_actions.hpp, vras_actions.hpp).  Shared by the
+// three and therefore not here: the header (aux_svc, aux_client_acked), the A word's first 14 bits (status .. rep_sent_sv), the bag word, and the A word of
+// replica r at 1 + (r - 1) * Model::wpr.
+struct WhereLayout {
+  const char* spec;        // the module, for messages
+  bool analysis;           // an analysis model: an entry is [operation |-> v], statuses Normal / ViewChange / StateTransfer, AnyDest, no clients
+  int peer_shift;          // rep_peer_op_number[r][p]: 2 bits at peer_shift + 2 (p - 1) of the A word
+  int noprog_shift;        // no_progress[r] in the A word, no_progress_ctr at bit 20 of the header; -1: the model has neither
+  int log_word, log_shift, log_width;   // rep_log[r]: in word aword(r) + log_word; 24 bits of entry bytes, or 9 bits of 3-bit entries
+  bool app_state;          // rep_app_state (A word, from bit 34) and rep_recv_dvc (the B word) exist
+};
+inline const WhereLayout& where_layout(int model_id) {
+  static const WhereLayout Y[3] = {{"VSR.tla", false, 19, -1, 1, 0, 24, false},
+                                   {"VR_STATE_TRANSFER.tla", true, 15, 14, 0, 25, 9, false},
+                                   {"VR_APP_STATE.tla", true, 15, 14, 0, 25, 9, true}};
+  return Y[model_id >= 0 && model_id <= 2 ? model_id : 0];
+}
 
 struct Compiler {
   const Model& M;
@@ -323,8 +370,11 @@ struct Compiler {
   int cur = 0, msg_depth = 0;
   bool step = false;                                          // a step predicate: step_action and the action names exist
   bool P = false;                                             // the loads being emitted read the successor (inside a primed expression)
+  const WhereLayout& Y;
+  const bool AN;                                              // an analysis model
 
-  Compiler(const Model& m, bool sym, const std::vector<std::string>& vals, WhereProgram& o) : M(m), symmetry(sym), values(vals), out(o) {}
+  Compiler(const Model& m, bool sym, const std::vector<std::string>& vals, WhereProgram& o)
+      : M(m), symmetry(sym), values(vals), out(o), Y(where_layout(m.model_id)), AN(Y.analysis) {}
 
   void emit(int code, u32 arg, int delta) {
     if (out.ops.size() + 1 >= (size_t)WHERE_MAX_OPS) throw Err{2, "state predicates: the program has more than " + std::to_string((int)WHERE_MAX_OPS) + " ops"};
@@ -362,7 +412,8 @@ struct Compiler {
       case N_ID: {
         if (const Binding* b = lookup(n->s)) { if (b->kind != 0) return false; *v = b->v; return true; }
         if (n->s == "ReplicaCount") { *v = M.R; return true; }
-        if (n->s == "ClientCount") { *v = M.C; return true; }
+        if (n->s == "ClientCount" && !AN) { *v = M.C; return true; }
+        if (n->s == "NoProgressChangeLimit" && AN) { *v = 0; return true; }                 // (the lowering accepts no other value)
         if (n->s == "StartViewOnTimerLimit") { *v = M.L; return true; }
         return false;
       }
@@ -434,6 +485,12 @@ struct Compiler {
     return root;
   }
   int entry_field(const NodeP& at, const std::string& f) {
+    if (AN) {                                                   // the entry is already its value + 1
+      if (f == "operation") return TY_VALUE;
+      if (f == "view_number" || f == "client_id" || f == "request_number")
+        fail(at, std::string("a log entry of ") + Y.spec + " is [operation |-> v]: it has no field " + f);
+      fail(at, "a log entry has no field " + f + " (operation)");
+    }
     const int k = f == "view_number" ? 0 : f == "operation" ? 1 : f == "client_id" ? 2 : f == "request_number" ? 3 : -1;
     if (k < 0) fail(at, "a log entry has no field " + f + " (view_number, operation, client_id, request_number)");
     emit(W_ENTF, (u32)k, 0);
@@ -441,10 +498,11 @@ struct Compiler {
   }
   void emit_log_len(const NodeP& r, bool lp) {                 // Len(rep_log[r])
     std::vector<int> vals;
-    indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 0, 24); emit(W_LOGLEN, 0, 0); }, lp);
+    indexed({Ix{r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift, Y.log_width); emit(W_LOGLEN, 0, 0); }, lp);
   }
   // rep_log[r] / rep_log'[r] as the argument of Len / DOMAIN: returns the index node r; *lp = the log is the successor's
   NodeP log_of(const NodeP& n, bool* lp) const {
+    if (AN) return nullptr;                                     // (seq_of, below)
     std::vector<Acc> acc;
     bool pr = false;
     NodeP root = flatten(n, acc);
@@ -452,6 +510,103 @@ struct Compiler {
     *lp = P || pr;
     if (root->k == N_ID && root->s == "rep_log" && !lookup("rep_log") && acc.size() == 1 && !acc[0].field) return acc[0].ix;
     return nullptr;
+  }
+
+  // ---- the analysis models ----------------------------------------------------------------------------------------------------------------------
+  // names the spec has (or VSR.tla has) but this model's lowering does not
+  void refuse_absent(const NodeP& at, const std::string& s) const {
+    if (!AN) return;
+    if (s == "clients" || s == "ClientCount" || s == "rep_client_table")
+      fail(at, s + ": " + Y.spec + " has no clients (a request is ReceiveClientRequest(r, v) for a value v)");
+    if (s == "rep_svc_recv" || s == "rep_dvc_recv")
+      fail(at, s + " is not a variable of " + Y.spec + (Y.app_state ? ": the DoViewChanges a replica holds are rep_recv_dvc[r]"
+                                                                     : ": the messages a replica has counted are the bag keys with messages[m] = 0"));
+    if (s == "Recovering") fail(at, std::string("Recovering is not a status of ") + Y.spec + " (Normal, ViewChange, StateTransfer)");
+    if (s == "aux_restart" || s == "rep_rec_number" || s == "rep_rec_recv" || s == "RecoveryMsg" || s == "RecoveryResponseMsg")
+      fail(at, s + " is never written under the cfg of " + Y.spec + ": the lowering does not store it");
+    if (s == "step_action") fail(at, std::string("step_action belongs to step predicates, which are not built for ") + Y.spec);
+  }
+  // a sequence of entries: 1 rep_log[r], 2 rep_app_state[r], 3 m.log of a bound message, 4 d.log of a held DoViewChange
+  struct Seq { int kind = 0; NodeP r; int loop = 0, dr = 0, ds = 0; };
+  bool seq_of(const NodeP& n, Seq* q) const {
+    std::vector<Acc> acc;
+    NodeP root = flatten(n, acc);
+    if (root->k != N_ID || acc.size() != 1) return false;
+    if (const Binding* b = lookup(root->s)) {
+      if (!acc[0].field || acc[0].name != "log") return false;
+      if (b->kind == 2) { q->kind = 3; q->loop = b->v; return true; }
+      if (b->kind == 3) { q->kind = 4; q->dr = b->v >> 4; q->ds = b->v & 15; return true; }
+      return false;
+    }
+    if (acc[0].field || defs.count(root->s)) return false;
+    q->r = acc[0].ix;
+    if (root->s == "rep_log") { q->kind = 1; return true; }
+    if (Y.app_state && root->s == "rep_app_state") { q->kind = 2; return true; }
+    return false;
+  }
+  int bword(int r) const { return aword(r) + 1; }              // rep_recv_dvc[r] (vras_actions.hpp)
+  static int dvc_shift(int s) { return 3 + 17 * (s - 1); }
+  void seq_len(const Seq& q) {
+    std::vector<int> vals;
+    switch (q.kind) {
+      case 1: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift, Y.log_width); emit(W_BLOGLEN, 0, 0); }, false); break;
+      case 2: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), 7, 2); }, false); break;   // Len(rep_app_state[r]) = rep_commit_number[r]
+      case 3: emit(W_MLOGLEN, (u32)q.loop, +1); break;
+      case 4: ldbits(bword(q.dr), dvc_shift(q.ds) + 8, 9); emit(W_BLOGLEN, 0, 0); break;
+    }
+  }
+  // entry i of the sequence in the one form every entry is compared in (value + 1, 0 = absent: outside the domain, or a replica out of range)
+  void seq_entry(const Seq& q, const NodeP& i) {
+    std::vector<int> vals;
+    switch (q.kind) {
+      case 1:
+        indexed({Ix{q.r, 1, M.R, TY_INT}, Ix{i, 1, 3, TY_INT}}, 0, vals, 0,
+                [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift + 3 * (v[1] - 1), 3); emit(W_ENTN, 0, 0); }, false);
+        break;
+      case 2:
+        indexed({Ix{q.r, 1, M.R, TY_INT}, Ix{i, 1, 3, TY_INT}}, 0, vals, 0, [&](const std::vector<int>& v) { emit(W_APPENT, (u32)aword(v[0]) | ((u32)v[1] << 8), +1); }, false);
+        break;
+      case 3: indexed({Ix{i, 1, 3, TY_INT}}, 0, vals, 0, [&](const std::vector<int>& v) { emit(W_MLOGENT, (u32)q.loop | ((u32)v[0] << 1), +1); }, false); break;
+      case 4:
+        indexed({Ix{i, 1, 3, TY_INT}}, 0, vals, 0,
+                [&](const std::vector<int>& v) { ldbits(bword(q.dr), dvc_shift(q.ds) + 8 + 3 * (v[0] - 1), 3); emit(W_ENTN, 0, 0); }, false);
+        break;
+    }
+  }
+  // x.log... with x a bound message or held DoViewChange: acc[0] is the field `log`
+  int compile_log_path(const NodeP& n, const std::vector<Acc>& acc, const Seq& q) {
+    if (acc.size() == 1)
+      fail(acc[0].at, "a whole log cannot be compared or used as a value: Len(x.log), x.log[i], x.log[i].operation, i \\in DOMAIN x.log and a quantifier over DOMAIN x.log are the supported forms");
+    if (acc[1].field || acc.size() > 3 || (acc.size() == 3 && !acc[2].field)) fail(n, "x.log[i] and x.log[i].operation are the supported forms");
+    seq_entry(q, acc[1].ix);
+    return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
+  }
+  // \A / \E d \in rep_recv_dvc[r]: unfolded over the source slots, each guarded by its present bit; a replica that is not a constant unfolds over replicas too
+  void quant_dvc(const NodeP& n, size_t var, const NodeP& r) {
+    const bool forall = n->s == "A";
+    auto slots = [&](int rv) {
+      for (int s = 1; s <= M.R; s++) {
+        ldbits(bword(rv), dvc_shift(s), 1);
+        env.push_back(Binding{n->vars[var], 3, (rv << 4) | s});
+        compile_quant(n, var + 1);
+        env.pop_back();
+        bin(forall ? W_IMP : W_AND);
+        if (s > 1) bin(forall ? W_AND : W_OR);
+      }
+    };
+    int rv;
+    if (const_int(r, &rv)) {
+      if (rv < 1 || rv > M.R) push(forall); else slots(rv);    // a replica out of range holds nothing
+      return;
+    }
+    for (rv = 1; rv <= M.R; rv++) {
+      want(r, compile(r), TY_INT);
+      push(rv);
+      bin(W_EQ);
+      slots(rv);
+      bin(forall ? W_IMP : W_AND);
+      if (rv > 1) bin(forall ? W_AND : W_OR);
+    }
   }
 
   int compile_path(const NodeP& n) {
@@ -470,12 +625,29 @@ struct Compiler {
     std::vector<int> vals;
     if (const Binding* b = lookup(s)) {
       if (root_primed) fail(n, s + " is a bound variable: it cannot be primed");
+      if (b->kind == 3) {                                       // a held DoViewChange of rep_recv_dvc[dr], from source ds
+        const int dr = b->v >> 4, ds = b->v & 15;
+        if (!acc[0].field) fail(acc[0].at, "a message cannot be indexed");
+        const std::string& f = acc[0].name;
+        if (f == "log") { Seq q; q.kind = 4; q.dr = dr; q.ds = ds; return compile_log_path(n, acc, q); }
+        if (acc.size() != 1) fail(n, s + "." + f + " has no fields and cannot be indexed");
+        if (f == "type") { push(T_DVC); return TY_MTYPE; }
+        if (f == "view_number") { ldbits(bword(dr), 0, 3); return TY_INT; }
+        if (f == "source") { push(ds); return TY_INT; }
+        if (f == "dest") { push(dr); return TY_INT; }
+        if (f == "last_normal_vn") { ldbits(bword(dr), dvc_shift(ds) + 1, 3); return TY_INT; }
+        if (f == "op_number") { ldbits(bword(dr), dvc_shift(ds) + 4, 2); return TY_INT; }
+        if (f == "commit_number") { ldbits(bword(dr), dvc_shift(ds) + 6, 2); return TY_INT; }
+        fail(acc[0].at, "a DoViewChangeMsg has no field " + f);
+      }
       if (b->kind != 2) fail(n, s + " is not a message: it has no fields and cannot be indexed");
       const int d = b->v;
       if (!acc[0].field) fail(acc[0].at, "a message cannot be indexed");
       const std::string& f = acc[0].name;
+      if (AN && f == "log") { Seq q; q.kind = 3; q.loop = d; return compile_log_path(n, acc, q); }
       if (f == "message") {
         emit(W_LDMENT, (u32)d, +1);
+        if (AN) emit(W_ENTN, 1, 0);
         if (acc.size() == 1) return TY_ENTRY;
         if (acc.size() == 2 && acc[1].field) return entry_field(acc[1].at, acc[1].name);
         fail(n, "m.message is a log entry: one field at most");
@@ -490,6 +662,7 @@ struct Compiler {
       fail(acc[0].at, "a message has no field " + f);
     }
     if (defs.count(s)) fail(n, s + " is a definition: it has no fields and cannot be indexed");
+    refuse_absent(root, s);
     if (s == "messages") {
       if (!shape({false})) fail(n, "messages[m] with m bound over DOMAIN messages is the supported form");
       const Binding* b = acc[0].ix->k == N_ID ? lookup(acc[0].ix->s) : nullptr;
@@ -509,12 +682,27 @@ struct Compiler {
         indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, e.type == TY_BOOL ? 0 : -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), e.shift, e.width); }, lp);
         return e.type;
       }
+    if (s == "no_progress" && Y.noprog_shift >= 0) {
+      if (!shape({false})) fail(n, s + "[r] is the supported form");
+      indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, 0, [&](const std::vector<int>& v) { ldbits(aword(v[0]), Y.noprog_shift, 1); }, lp);
+      return TY_BOOL;
+    }
     if (s == "rep_peer_op_number") {
       if (!shape({false, false})) fail(n, "rep_peer_op_number[r][p] is the supported form");
       indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, M.R, TY_INT}}, 0, vals, -1,
-              [&](const std::vector<int>& v) { ldbits(aword(v[0]), 19 + 2 * (v[1] - 1), 2); }, lp);
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]), Y.peer_shift + 2 * (v[1] - 1), 2); }, lp);
       return TY_INT;
     }
+    if (AN && (s == "rep_log" || (Y.app_state && s == "rep_app_state"))) {
+      if (!shape({false, false}) && !shape({false, false, true}))
+        fail(n, s + "[r][i], its .operation, Len(" + s + "[r]) and DOMAIN " + s + "[r] are the supported forms");
+      Seq q;
+      q.kind = s == "rep_log" ? 1 : 2;
+      q.r = acc[0].ix;
+      seq_entry(q, acc[1].ix);
+      return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
+    }
+    if (Y.app_state && s == "rep_recv_dvc") fail(n, "rep_recv_dvc: Cardinality(rep_recv_dvc[r]) and \\A / \\E d \\in rep_recv_dvc[r] are the supported forms");
     if (s == "rep_client_table") {
       if (!shape({false, false, true})) fail(n, "rep_client_table[r][c].request_number / .op_number / .executed are the supported forms");
       const std::string& f = acc[2].name;
@@ -527,7 +715,7 @@ struct Compiler {
     if (s == "rep_log") {
       if (!shape({false, false}) && !shape({false, false, true})) fail(n, "rep_log[r][i], its fields, Len(rep_log[r]) and DOMAIN rep_log[r] are the supported forms");
       indexed({Ix{acc[0].ix, 1, M.R, TY_INT}, Ix{acc[1].ix, 1, 3, TY_INT}}, 0, vals, 0,      // outside the log: the absent entry
-              [&](const std::vector<int>& v) { ldbits(aword(v[0]) + 1, 8 * (v[1] - 1), 8); }, lp);
+              [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift + 8 * (v[1] - 1), 8); }, lp);
       return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
     }
     if (s == "aux_client_acked") {
@@ -544,6 +732,7 @@ struct Compiler {
   bool const_set(const NodeP& s, int* lo, int* hi, int* kind) {
     *kind = 0;
     if (s->k == N_ID && !lookup(s->s) && !defs.count(s->s)) {
+      refuse_absent(s, s->s);
       if (s->s == "replicas") { *lo = 1; *hi = M.R; return true; }
       if (s->s == "clients") { *lo = 1; *hi = M.C; return true; }
       if (s->s == "Values") { *lo = 1; *hi = M.n; *kind = 1; return true; }
@@ -572,6 +761,26 @@ struct Compiler {
         env.pop_back();
         if (k > lo) bin(forall ? W_AND : W_OR);
       }
+      return TY_BOOL;
+    }
+    Seq q;
+    if (AN && set->k == N_DOMAIN && seq_of(set->c[0], &q)) {          // the domain of a sequence: unfolded over the three positions, each guarded by its presence
+      for (int k = 1; k <= 3; k++) {
+        NodeP kn = std::make_shared<Node>();
+        kn->k = N_NUM; kn->v = k; kn->line = set->line; kn->col = set->col;
+        seq_entry(q, kn);
+        push(0);
+        bin(W_NE);
+        env.push_back(Binding{name, 0, k});
+        compile_quant(n, var + 1);
+        env.pop_back();
+        bin(forall ? W_IMP : W_AND);
+        if (k > 1) bin(forall ? W_AND : W_OR);
+      }
+      return TY_BOOL;
+    }
+    if (Y.app_state && set->k == N_INDEX && set->c[0]->k == N_ID && set->c[0]->s == "rep_recv_dvc" && !lookup("rep_recv_dvc") && !defs.count("rep_recv_dvc")) {
+      quant_dvc(n, var, set->c[1]);
       return TY_BOOL;
     }
     if (set->k == N_DOMAIN && (logr = log_of(set->c[0], &loglp))) {    // 1..Len(rep_log[r]): unfolded over the three positions, each guarded by its presence
@@ -603,6 +812,12 @@ struct Compiler {
       emit(W_MEND, (u32)d | ((u32)forall << 1) | ((u32)(begin + 1) << 2) | ((u32)pr << 14), 0);
       msg_depth--;
       return TY_BOOL;
+    }
+    if (AN) {
+      const NodeP inner = set->k == N_DOMAIN ? set->c[0] : set;
+      if (inner->k == N_INDEX || inner->k == N_FIELD) compile(inner);   // (an unknown or refused name says so itself)
+      fail(set, std::string("a quantifier ranges over replicas, Values, a..b, DOMAIN messages, DOMAIN rep_log[r], DOMAIN m.log") +
+                    (Y.app_state ? ", DOMAIN rep_app_state[r], rep_recv_dvc[r] or DOMAIN d.log" : ""));
     }
     fail(set, "a quantifier ranges over replicas, clients, Values, a..b, DOMAIN rep_log[r] or DOMAIN messages");
   }
@@ -678,6 +893,26 @@ struct Compiler {
         const NodeP& a = n->c[0];
         int v;
         if (const_int(n, &v)) { push(v); return TY_INT; }
+        if (AN) {
+          Seq q;
+          std::vector<Acc> acc;
+          NodeP root = flatten(a, acc);
+          if (n->s == "Len") {
+            if (seq_of(a, &q)) { seq_len(q); return TY_INT; }
+          } else if (Y.app_state && root->k == N_ID && root->s == "rep_recv_dvc" && !lookup(root->s) && !defs.count(root->s) && acc.size() == 1 && !acc[0].field) {
+            std::vector<int> vals;
+            indexed({Ix{acc[0].ix, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& r) {
+              for (int s = 1; s <= M.R; s++) {
+                ldbits(bword(r[0]), dvc_shift(s), 1);
+                if (s > 1) bin(W_ADD);
+              }
+            }, false);
+            return TY_INT;
+          }
+          if (a->k == N_INDEX || a->k == N_FIELD || a->k == N_ID) compile(a);   // (an unknown or refused name says so itself)
+          fail(n, std::string("Len of rep_log[r], m.log") + (Y.app_state ? ", rep_app_state[r], d.log; Cardinality(Values) and Cardinality(rep_recv_dvc[r])" : "; Cardinality(Values)") +
+                      " are the supported forms");
+        }
         if (n->s == "Len") {
           bool lp = false;
           NodeP r = log_of(a, &lp);
@@ -707,6 +942,7 @@ struct Compiler {
         const std::string& s = n->s;
         if (const Binding* b = lookup(s)) {
           if (b->kind == 2) fail(n, "a message is used through its fields (" + s + ".type, messages[" + s + "], ...)");
+          if (b->kind == 3) fail(n, "a held DoViewChange is used through its fields (" + s + ".source, " + s + ".log[i], ...)");
           push(b->v);
           return b->kind == 1 ? TY_VALUE : TY_INT;
         }
@@ -723,6 +959,13 @@ struct Compiler {
         if (s == compiling) fail(n, s + " refers to itself");
         int v;
         if (const_int(n, &v)) { push(v); return TY_INT; }
+        if (AN) {
+          refuse_absent(n, s);
+          if (s == "StateTransfer") { push(2); return TY_STATUS; }  // vrst::ST2_STATETRANSFER
+          if (s == "AnyDest") { push(7); return TY_INT; }           // vrst::ANYDEST: what m.dest reads; no replica has this number
+          if (s == "no_progress_ctr") { ldbits(0, 20, 3); return TY_INT; }
+          if (s == "no_progress" || (Y.app_state && (s == "rep_app_state" || s == "rep_recv_dvc"))) fail(n, s + " is a function: apply it to an index");
+        }
         static const struct { const char* name; int code, type; } K[] = {
             {"Normal", ST_NORMAL, TY_STATUS}, {"ViewChange", ST_VIEWCHANGE, TY_STATUS}, {"Recovering", ST_RECOVERING, TY_STATUS},
             {"StartViewChangeMsg", T_SVC, TY_MTYPE}, {"PrepareMsg", T_PREPARE, TY_MTYPE}, {"PrepareOkMsg", T_PREPAREOK, TY_MTYPE},
@@ -795,6 +1038,13 @@ struct Compiler {
           }
           if (dom && dom->k == N_ID && dom->s == "messages" && !lookup("messages"))
             fail(set, "\\in DOMAIN messages as a test would search the bag: quantify over it instead (a message of one bag cannot be looked up in the other)");
+          Seq q;
+          if (AN && set->k == N_DOMAIN && seq_of(set->c[0], &q)) {      // i \in DOMAIN s  ==  entry i of s is there (out of 1..3: the absent entry)
+            seq_entry(q, n->c[0]);
+            push(0);
+            bin(W_NE);
+            return TY_BOOL;
+          }
           if (const_set(set, &lo, &hi, &kind)) {
             want(n->c[0], compile(n->c[0]), kind ? TY_VALUE : TY_INT);
             push(lo); bin(W_GE);
@@ -811,6 +1061,11 @@ struct Compiler {
             bin(W_LE);
             bin(W_AND);
             return TY_BOOL;
+          }
+          if (AN) {
+            const NodeP inner = set->k == N_DOMAIN ? set->c[0] : set;
+            if (inner->k == N_INDEX || inner->k == N_FIELD) compile(inner);
+            fail(set, "\\in is supported for replicas, Values, a..b, DOMAIN aux_client_acked and the domain of a log (rep_log[r], m.log, ...)");
           }
           fail(set, "\\in is supported for replicas, clients, Values, a..b, DOMAIN rep_log[r] and DOMAIN aux_client_acked");
         }

@@ -34,7 +34,8 @@ static void usage() {
       "  -terminalReport   scan every stored level for terminal states without stopping; one summary line at the end.  A terminal state in\n"
       "                    which AllReplicasMoveToSameView is false is printed with its behaviour (last line: Stuttering): a counter-example\n"
       "                    to ViewChangeCompletes.  Finding none is no verdict: behaviours that loop are not examined\n"
-      "  -predicates FILE  state predicates in TLA+ syntax (VSR.tla only; the language: csrc/vsr_where_parse.hpp, an example: tools/predicates_example.txt):\n"
+      "  -predicates FILE  state predicates in TLA+ syntax, for any loaded cfg (the language: csrc/vsr_where_parse.hpp; examples: tools/predicates_example.txt,\n"
+      "                    tools/predicates_model2_example.txt, tools/predicates_model3_example.txt):\n"
       "                    one expression, or definitions Name == expr (at most 8 that are not LOCAL).  Used by:\n"
       "  -reach NAME[,NAME]      every stored level is scanned before it is expanded; the first level with a state that satisfies NAME ends the run:\n"
       "                    \"State satisfying NAME found at depth d\" and the behaviour into the one with the smallest fingerprint (a shortest one;\n"
@@ -346,7 +347,7 @@ int main(int argc, char** argv) {
     std::stringstream pss;
     pss << pf.rdbuf();
     const std::string text = pss.str();
-    if (vsrmc_where_compile(m, text.c_str(), &w_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", predicates_file.c_str(), vsrmc_last_error()); return 1; }
+    if (vsrmc_predicates_compile(m, text.c_str(), &w_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", predicates_file.c_str(), vsrmc_last_error()); return 1; }
     vsrmc_where_desc wd;
     vsrmc_where_describe(w_all, &wd);
     for (int k = 0; k < wd.n_names; k++) where_names.push_back(wd.names[k]);
@@ -361,7 +362,7 @@ int main(int argc, char** argv) {
         if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", predicates_file.c_str(), query_names[k].c_str()); return 2; }
         local += "\nQuery" + std::to_string(k) + " == " + (k < n_reach ? "" : "~") + query_names[k];
       }
-      if (vsrmc_where_compile(m, local.c_str(), &w_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+      if (vsrmc_predicates_compile(m, local.c_str(), &w_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
   }
   vsrmc_options o;
