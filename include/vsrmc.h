@@ -334,7 +334,7 @@ int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_wher
 int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_where_info* out);
 int32_t vsrmc_checker_where_states(vsrmc_checker* c, uint64_t* fps, uint8_t* bits, uint64_t cap, uint64_t* n);
 
-/* ---- step predicates: user-written predicates over a state AND its successor, checked on every transition (VSR.tla only) ------
+/* ---- step predicates: user-written predicates over a state AND its successor, checked on every transition -------------------------
  * The safety half of PROPERTY: an action property [][P]_vars is a predicate over a (state, successor) pair.  The language of the state predicates
  * plus primed variables (rep_view_number'[r], Len(rep_log[r])', (...)', \A m \in DOMAIN messages', messages'[m]), UNCHANGED e and step_action (the
  * Next disjunct that produced the pair — not TLA+) — csrc/vsr_where_parse.hpp specifies it, what is refused, and where it departs from TLC: the
@@ -343,7 +343,12 @@ int32_t vsrmc_checker_where_states(vsrmc_checker* c, uint64_t* fps, uint8_t* bit
  * vsrmc_step_compile: needs no device.  A text without primes compiles to exactly the ops vsrmc_where_compile gives it; the program carries a step
  *   flag (vsrmc_where_desc.step).  vsrmc_where_compile keeps refusing primes; vsrmc_where_batch / vsrmc_checker_where_scan refuse a step program
  *   (VSRMC_E_ARG), vsrmc_step_batch / vsrmc_checker_step_scan a state program.  The same caps: 4096 ops, depth 32, 8 exports.  Destroyed and
- *   described by vsrmc_where_destroy / vsrmc_where_describe.
+ *   described by vsrmc_where_destroy / vsrmc_where_describe.  Models 2 and 3: "step predicates: VSR.tla only".
+ * vsrmc_step_predicates_compile: the model-generic entry, as vsrmc_predicates_compile is for states.  For a VSR.tla model it returns exactly what
+ *   vsrmc_step_compile returns, op for op; for a model of vsrmc_model2_from_constants / vsrmc_model3_from_constants (or their cfgs) it compiles the step
+ *   language over that spec's variables (rep_log'[r], no_progress'[r], \A m \in DOMAIN messages' with m.log; on VR_APP_STATE.tla also rep_app_state'[r],
+ *   Cardinality(rep_recv_dvc[r])' and \A d \in rep_recv_dvc'[r] — csrc/vsr_where_parse.hpp).  The program records its model and the step flag: every
+ *   call below takes it unchanged, and it is refused by any model but its own and by the state entry points.
  * vsrmc_step_batch: n wire records of the caller -> one row of five words per generated successor, in (parent, ordinal) order — the rows of
  *   vsrmc_expand_batch over the same batch, row for row: [parent, ordinal, action id, bits, error code].  An instance whose action raises an
  *   evaluation error (error code != 0) is not evaluated: its bits are 0.  rows == NULL asks for the number.
@@ -371,6 +376,7 @@ typedef struct vsrmc_step_info {
   uint64_t slices;                                 /* launches of k_step_list (slices run again in halves included) */
 } vsrmc_step_info;
 int32_t vsrmc_step_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
+int32_t vsrmc_step_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out);
 int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint64_t* rows,
                          uint64_t cap_rows, uint64_t* n_rows);
 int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_step_info* out);

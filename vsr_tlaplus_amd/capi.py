@@ -143,6 +143,7 @@ SYMBOLS = {
     "vsrmc_checker_where_scan": (C.c_int32, [V, V, C.POINTER(WhereInfo)]),
     "vsrmc_checker_where_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_step_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
+    "vsrmc_step_predicates_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_checker_step_scan": (C.c_int32, [V, V, C.POINTER(StepInfo)]),
     "vsrmc_checker_step_successor": (C.c_int32, [V, C.c_uint64, C.c_uint32, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),

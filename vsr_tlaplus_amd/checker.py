@@ -193,6 +193,14 @@ class Model:
         check(capi.load().vsrmc_step_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
         return Where(h, self)
 
+    def compile_step_predicates(self, text):
+        """Step predicates for ANY model -> Where with step == True.  A VSR.tla model: exactly compile_step's program.  second_model / third_model: the
+        step language over that spec's variables (csrc/vsr_where_parse.hpp).  Needs no device.  Raises VsrmcError with "line:col: reason" for a text
+        that is refused."""
+        h = C.c_void_p()
+        check(capi.load().vsrmc_step_predicates_compile(self._h, text.encode() if isinstance(text, str) else text, C.byref(h)))
+        return Where(h, self)
+
     def step_flags(self, w, words, off, device=0):
         """The step predicates of `w` on every transition out of a batch of states (k_step_list, k_step_apply) -> an (n, 5) uint64 array, one row
         [parent, ordinal, action, bits, err] per generated successor in (parent, ordinal) order: the rows of get_next_states, row for row.  A row
@@ -551,7 +559,7 @@ class ModelChecker:
         reach / never (a Where each, off by default): every stored level is scanned (k_where) before it is expanded, where check_deadlock scans.  The
         first level with a state that satisfies a predicate of `reach` ends the run with "reached"; one that satisfies a predicate of `never` (the
         negation of a user's invariant) ends it with "violation".  self.witness = dict(level, k, name, fp, index, kind); witness_trace() the behaviour.
-        step_never / step_reach (a step Where each — Model.compile_step — off by default): every stored level is step-scanned (step_scan: every
+        step_never / step_reach (a step Where each — Model.compile_step / compile_step_predicates — off by default): every stored level is step-scanned (step_scan: every
         transition out of it) before it is expanded, after the scans above.  A pair that satisfies a predicate of step_never ends the run with
         "violation", one that satisfies step_reach with "reached"; self.witness then names the PARENT (level, fp, index) and has `ordinal` and
         `action` besides; step_witness_trace() is the behaviour with the step at its end."""

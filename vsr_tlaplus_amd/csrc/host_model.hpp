@@ -446,13 +446,7 @@ int32_t vsrmc_model_format_state(const vsrmc_model* m, const uint64_t* rec, char
   return 0;
 }
 
-const char* vsrmc_action_name(int32_t a) {
-  static const char* const NAMES[16] = {"Initial predicate", "TimerSendSVC", "ReceiveHigherSVC", "ReceiveMatchingSVC",
-                                        "SendDVC", "ReceiveHigherDVC", "ReceiveMatchingDVC", "SendSV", "ReceiveSV",
-                                        "ReceiveClientRequest", "ReceivePrepareMsg", "ReceivePrepareOkMsg", "ExecuteOp",
-                                        "SendGetState", "ReceiveGetState", "ReceiveNewState"};   // VSR.tla:896-913
-  return (a >= 0 && a < 16) ? NAMES[a] : "?";
-}
+const char* vsrmc_action_name(int32_t a) { return action_name((int)a); }
 
 void vsrmc_model_destroy(vsrmc_model* m) { delete m; }
 

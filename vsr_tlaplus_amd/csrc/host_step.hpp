@@ -1,4 +1,5 @@
-// host_step.hpp — step predicates: the host side of k_step_list / k_step_apply (vsr_step.hpp) — compiling a text with primes (vsr_where_parse.hpp), a
+// host_step.hpp — step predicates: the host side of k_step_list / k_step_apply (vsr_step.hpp) — compiling a text with primes (vsr_where_parse.hpp;
+// vsrmc_step_predicates_compile for any model, vsrmc_step_compile for VSR.tla alone), picking the model's instantiation, a
 // caller's batch, the scan of the checker's newest stored level over slices, the hit pairs the last scan left (included by vsrmc.hip: one translation
 // unit, the sections share its anonymous-namespace helpers).
 #pragma once
@@ -55,6 +56,9 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
   HIPCHK(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(b.prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
   HIPCHK(hipStreamSynchronize(stream));
+  // (where_fits: the program is this model's)
+  auto* const list_kernel = M.model_id == 1 ? k_step_list<1> : M.model_id == 2 ? k_step_list<2> : k_step_list<0>;
+  auto* const apply_kernel = M.model_id == 1 ? k_step_apply<1> : M.model_id == 2 ? k_step_apply<2> : k_step_apply<0>;
   u64 scanned = 0;
   slice = std::max<u64>(1, slice);
   const u64 slice0 = slice;
@@ -63,7 +67,7 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
     HIPCHK(hipMemsetAsync(b.ctl, 0, 16, stream));                  // n_list, scanned: of this slice
     const unsigned grid_l = (unsigned)std::max<u64>(1, std::min<u64>((end - pos + 255) / 256, (u64)num_cus * 8));
     HIPCHK(hipEventRecord(b.ev[0], stream));
-    hipLaunchKernelGGL(k_step_list, dim3(grid_l), dim3(256), 0, stream, M, d_words, d_refs, pos, end, b.list, list_cap, b.ctl);
+    hipLaunchKernelGGL(list_kernel, dim3(grid_l), dim3(256), 0, stream, M, d_words, d_refs, pos, end, b.list, list_cap, b.ctl);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(b.ev[1], stream));
     u64 head[2] = {0, 0};
@@ -84,7 +88,7 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
     if (head[0]) {
       const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)num_cus * 8));
       HIPCHK(hipEventRecord(b.ev[2], stream));
-      hipLaunchKernelGGL(k_step_apply, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, (const u64*)b.list,
+      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, (const u64*)b.list,
                          head[0], b.ctl, d_fps ? b.hits : nullptr, hit_cap, b.rows);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(b.ev[3], stream));
@@ -130,11 +134,28 @@ int32_t vsrmc_step_compile(const vsrmc_model* m, const char* text, vsrmc_where**
   return 0;
 }
 
+// the model-generic entry: VSR.tla -> what vsrmc_step_compile gives, op for op; the analysis models -> the step language over their own variable table
+int32_t vsrmc_step_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out) {
+  if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
+  if (m->M.model_id == 0) return vsrmc_step_compile(m, text, out);
+  *out = nullptr;
+  vsrmc_where* w = new vsrmc_where();
+  std::string err;
+  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err, true);
+  if (rc) {
+    delete w;
+    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
+  }
+  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry; w->model_id = m->M.model_id;
+  *out = w;
+  return 0;
+}
+
 int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint64_t* rows,
                          uint64_t cap_rows, uint64_t* n_rows) {
   if (!m || !w || !words || !off || !n_rows) return fail(VSRMC_E_ARG, "NULL argument");
   *n_rows = 0;
-  if (!w->prog.step) return fail(VSRMC_E_ARG, "step predicates: the program was compiled by vsrmc_where_compile (vsrmc_step_compile compiles a step program)");
+  if (!w->prog.step) return fail(VSRMC_E_ARG, "step predicates: the program was compiled by vsrmc_where_compile (vsrmc_step_compile / vsrmc_step_predicates_compile compile a step program)");
   if (!where_fits(w, m->M, m->symmetry)) return fail(VSRMC_E_ARG, "step predicates: compiled for another model");
   int rc = check_device(device);
   if (rc) return rc;
@@ -194,7 +215,7 @@ int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_st
   std::memset(out, 0, sizeof(*out));
   out->level = c->level;
   for (int k = 0; k < WHERE_MAX_EXPORTS; k++) { out->min_fp[k] = out->min_index[k] = ~(u64)0; out->min_ordinal[k] = ~(uint32_t)0; out->min_action[k] = -1; }
-  if (!w->prog.step) return fail(VSRMC_E_ARG, "step predicates: the program was compiled by vsrmc_where_compile (vsrmc_step_compile compiles a step program)");
+  if (!w->prog.step) return fail(VSRMC_E_ARG, "step predicates: the program was compiled by vsrmc_where_compile (vsrmc_step_compile / vsrmc_step_predicates_compile compile a step program)");
   if (!where_fits(w, c->model.M, c->model.symmetry)) return fail(VSRMC_E_ARG, "step predicates: compiled for another model");
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "step scan: sharded checkers are not scanned");
   if (c->deep || c->deep_regen_done || c->full_recoverable)

@@ -45,6 +45,15 @@ enum {
   A_ReceiveMatchingDVC, A_SendSV, A_ReceiveSV, A_ReceiveClientRequest, A_ReceivePrepareMsg, A_ReceivePrepareOkMsg,
   A_ExecuteOp, A_SendGetState, A_ReceiveGetState, A_ReceiveNewState, A_COUNT
 };
+// The names traces print (VSR.tla:896-913; the two analysis specs name their Next disjuncts the same): the one table behind vsrmc_action_name and the
+// action constants of step predicates (vsr_where_parse.hpp).
+inline const char* action_name(int a) {
+  static const char* const NAMES[A_COUNT] = {"Initial predicate", "TimerSendSVC", "ReceiveHigherSVC", "ReceiveMatchingSVC",
+                                             "SendDVC", "ReceiveHigherDVC", "ReceiveMatchingDVC", "SendSV", "ReceiveSV",
+                                             "ReceiveClientRequest", "ReceivePrepareMsg", "ReceivePrepareOkMsg", "ExecuteOp",
+                                             "SendGetState", "ReceiveGetState", "ReceiveNewState"};
+  return (a >= 0 && a < A_COUNT) ? NAMES[a] : "?";
+}
 
 // Error codes raised by the device path (first one wins; the run aborts like a TLC evaluation error would).
 enum {

@@ -1,16 +1,18 @@
 // vsr_step.hpp — step predicates: user-written predicates over a state AND its successor (primed variables, UNCHANGED, step_action; compiled by
-// vsr_where_parse.hpp's step entry) evaluated on every transition out of the records of a level.  VSR.tla only.
+// vsr_where_parse.hpp's step entry) evaluated on every transition out of the records of a level (§9e for the two analysis models).  One
+// instantiation of each kernel per model, as k_where<MODEL>: <0> is VSR.tla's and compiles what it compiled before.
 //
 // The interpreter (where_run, vsr_where.hpp) needs a wave-uniform program counter and wants its lanes busy.  A record has M.m0 + nmsg * (R + 1) ordinals
 // of which a handful are enabled, so a lane-per-parent loop over ordinals would run the program with most lanes idle.  Two kernels instead, run by the
 // host over slices of the level (host_step.hpp):
 //
-//   k_step_list   one lane per parent record (refs[i] == 0 = a hole): guards only — guard_slot_pre, the statement k_terminal and k_expand's enumeration
-//                 use — and every enabled instance appended as parent index | ordinal << 40 to a global list, wave-aggregated (one atomic per wave and
+//   k_step_list   one lane per parent record (refs[i] == 0 = a hole): guards only — ModelOps<MODEL>::guard_pre, the statement k_terminal and k_expand's
+//                 enumeration use — and every enabled instance appended as parent index | ordinal << 40 to a global list, wave-aggregated (one atomic per wave and
 //                 round: wave_alloc).  The wave walks the slots together, so that the lanes that have an instance in a round allocate together.
-//   k_step_apply  one lane per list entry: gen<false> on the parent gives the Delta; an entry whose action raises an evaluation error (D.err) is counted
+//   k_step_apply  one lane per list entry: ModelOps<MODEL>::gen_<false> on the parent gives the Delta; an entry whose action raises an evaluation error (D.err) is counted
 //                 and not evaluated.  The program then runs over a PAIR VIEW of (parent record, Delta) — no child record is written anywhere:
-//                   word w of the child   = D.hdr for w = 0, D.rep[w - base] inside the block of replica D.r, the parent's word otherwise;
+//                   word w of the child   = D.hdr for w = 0, D.rep[w - base] inside the block of replica D.r (w - base < wpr: a block of the analysis
+//                                           models has one or two words, and the word after it is the NEXT replica's), the parent's word otherwise;
 //                   bag entry j of the child = for j < the parent's nmsg the parent's entry, replaced by D.pnew[s] where patch slot s names j;
 //                                           beyond that the appended slots in slot order (the order write_child_serial writes them).
 //                 D.rep and D.pnew are picked by unrolled selects, never by a run-time subscript, so that the Delta stays in registers.  The operand stack
@@ -21,12 +23,13 @@
 // (parent fingerprint, parent index, ordinal, bits) quadruple appended wave-wise to a list of which the first hit_cap that arrive are kept
 // (StepCtl::n_hits = the true number).  `rows`, when given (a caller's batch), receives action | bits << 8 | err << 16 per list entry.
 #pragma once
-#include "vsr_actions.hpp"
+#include "vsr_kernels.hpp"
 #include "vsr_where.hpp"
 
 namespace vsr {
 
 // the successor as where_run sees it: the parent record and the Delta of one instance (host-callable like where_run itself)
+template <int MODEL>
 struct StepPair {
   static constexpr bool is_pair = true;
   const u64* rec;
@@ -35,7 +38,8 @@ struct StepPair {
   VSR_HD u64 word(int w) const {
     const int k = w - rbase;
     u64 v = rec[w];
-    v = k == 0 ? D.rep[0] : k == 1 ? D.rep[1] : k == 2 ? D.rep[2] : (k == 3 && wpr > 3) ? D.rep[3] : v;
+    // every substitution needs k < wpr; VSR.tla's blocks have 3 or 4 words, so its first three need no test
+    v = k == 0 ? D.rep[0] : (k == 1 && (MODEL == 0 || wpr > 1)) ? D.rep[1] : (k == 2 && (MODEL == 0 || wpr > 2)) ? D.rep[2] : (k == 3 && wpr > 3) ? D.rep[3] : v;
     return w == 0 ? D.hdr : v;
   }
   VSR_HD u64 msg(int j) const {
@@ -65,6 +69,7 @@ struct StepCtl {
   u64 n_hits;                         // pairs with any bit set offered to the hit list
 };
 
+template <int MODEL>
 __global__ void __launch_bounds__(256)
 k_step_list(Model M, const u64* __restrict__ words, const u64* __restrict__ refs, u64 lo, u64 hi, u64* list, u64 list_cap, StepCtl* ctl) {
   u32 n_scanned = 0;
@@ -92,8 +97,8 @@ k_step_list(Model M, const u64* __restrict__ words, const u64* __restrict__ refs
     wslots = (int)VSR_WHERE_UNI(wslots);
     for (int slot = 0; slot < wslots; slot++) {
       int kind0 = 0;
-      u32 mask = slot < nslots ? guard_slot_pre(M, rec, hdr, Areg, slot, &kind0) : 0u;
-      while (__ballot(mask != 0) != 0) {                           // (wave-uniform) bit k of a message slot: k = 0 the receive, k = d SendGetState(r, d, m)
+      u32 mask = slot < nslots ? ModelOps<MODEL>::guard_pre(M, rec, hdr, Areg, slot, &kind0, -1) : 0u;
+      while (__ballot(mask != 0) != 0) {                           // (wave-uniform) bit k of a message slot: k = 0 the receive, k = d SendGetState(r, d, m) (AnyDest: replica d receives)
         if (mask != 0) {
           const int k = __ffs((int)mask) - 1;
           mask &= mask - 1;
@@ -107,6 +112,7 @@ k_step_list(Model M, const u64* __restrict__ words, const u64* __restrict__ refs
   if (lane_id() == 0 && n_scanned) atomicAdd((unsigned long long*)&ctl->scanned, (unsigned long long)n_scanned);
 }
 
+template <int MODEL>
 __global__ void __launch_bounds__(256)
 k_step_apply(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restrict__ words, const u64* __restrict__ refs, const u64* __restrict__ fps,
              const u64* __restrict__ list, u64 n_entries, StepCtl* ctl, u64* hits, u64 hit_cap, u32* rows) {
@@ -127,7 +133,7 @@ k_step_apply(Model M, const u32* __restrict__ prog, int n_exports, const u64* __
     const u64* rec = words + (ref >> 8);
     Delta D = Delta();
     bool enabled = false;
-    if (have) enabled = gen<false>(M, rec, ord, D);
+    if (have) enabled = ModelOps<MODEL>::template gen_<false>(M, rec, ord, D);
     const bool err = have && enabled && D.err != 0;
     const bool valid = have && enabled && D.err == 0;
     const int nmsg_p = valid ? hdr_nmsg(rec[0]) : 0, nmsg_c = valid ? hdr_nmsg(D.hdr) : 0;
@@ -135,8 +141,8 @@ k_step_apply(Model M, const u32* __restrict__ prog, int n_exports, const u64* __
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
     wmax = (int)VSR_WHERE_UNI(wmax);
-    const StepPair pair{rec, D, M.fixed, 1 + ((int)D.r - 1) * M.wpr, M.wpr, nmsg_p, nmsg_c, (int)D.action};
-    const u32 raw = where_run(prog, M.fixed, rec, valid, nmsg_p, wmax, S, pair);
+    const StepPair<MODEL> pair{rec, D, M.fixed, 1 + ((int)D.r - 1) * M.wpr, M.wpr, nmsg_p, nmsg_c, (int)D.action};
+    const u32 raw = where_run<WhereLdsStack, const u64*, StepPair<MODEL>, MODEL>(prog, M.fixed, rec, valid, nmsg_p, wmax, S, pair);
     const u32 bits = valid ? raw : 0;                              // (a lane without a pair ran the program over zeros: TRUE would count it)
     if (rows && have) rows[e] = (u32)D.action | (bits << 8) | ((u32)(D.err & 0xFF) << 16) | (enabled ? 0u : 1u << 31);
     n_pairs += (u32)__popcll(__ballot(valid));

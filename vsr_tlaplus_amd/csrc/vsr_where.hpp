@@ -45,7 +45,8 @@ enum {
   W_MLOGENT,   // arg: loop(1) | i(2) << 1, i in 1..3 : m.log[i] normalised — of a DoViewChangeMsg / StartViewMsg the sequence's entry i, of a NewStateMsg the
                // entry i with first_op <= i <= op_number, 0 for every other type and outside the domain
   W_MLOGLEN,   // arg: loop : the number of entries m.log holds (the sum of W_MLOGENT != 0 over i)
-  W_APPENT,    // arg: word(8) | i(2) << 8 : rep_app_state[r][i] normalised, read from the A word rec[word]: present iff i <= commit number (model 2)
+  W_APPENT,    // arg: word(8) | i(2) << 8 | primed(1) << 20 : rep_app_state[r][i] normalised, read from the A word rec[word] (primed, step programs only: of the
+               // child's word — entry and commit number of the same side): present iff i <= commit number (model 2)
   W_OPCOUNT
 };
 enum { WHERE_MAX_OPS = 4096, WHERE_MAX_DEPTH = 32, WHERE_MAX_EXPORTS = 8 };
@@ -73,7 +74,8 @@ VSR_HD int where_mlog_entry(u64 w, int i) {
   return (in_dom && (b & 7)) ? ((b >> 3) & 3) + 1 : 0;
 }
 
-// MODEL: the model id the program was compiled for.  0 (VSR.tla, and every step program) compiles none of the analysis models' ops.
+// MODEL: the model id the program was compiled for.  0 (VSR.tla) compiles none of the analysis models' ops.  W_MLOGENT / W_MLOGLEN read the loop's current bag word,
+// whichever bag the loop runs over; W_ENTN and W_BLOGLEN work on the value on top: the four are the same in a step program.
 template <typename STACK, typename PTR, typename PAIR = WhereNoPair, int MODEL = 0>
 VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool valid, int nmsg, int wmax, STACK& S, const PAIR& pair = PAIR()) {
   u32 bits = 0;
@@ -180,7 +182,8 @@ VSR_HD u32 where_run(const u32* __restrict__ prog, int fixed, PTR rec, bool vali
               const u64 w = (arg & 1) ? mw1 : mw0;
               S[sp++] = (where_mlog_entry(w, 1) != 0) + (where_mlog_entry(w, 2) != 0) + (where_mlog_entry(w, 3) != 0);
             } else {                                                  // W_APPENT
-              const u64 A = valid ? rec[arg & 0xFF] : (u64)0;
+              u64 A = valid ? rec[arg & 0xFF] : (u64)0;
+              if constexpr (PAIR::is_pair) { if (valid && ((arg >> 20) & 1)) A = pair.word((int)(arg & 0xFF)); }
               const int i = (int)((arg >> 8) & 3);
               S[sp++] = i <= a_commit(A) ? (int)((A >> (34 + 2 * (i - 1))) & 3) + 1 : 0;
             }

@@ -57,8 +57,8 @@
 //               On VR_STATE_TRANSFER.tla rep_app_state and rep_recv_dvc are unknown identifiers: there the DoViewChanges a replica has counted are the bag
 //               keys with messages[m] = 0.
 // Refused with a reason that names the model: clients ClientCount rep_client_table rep_svc_recv rep_dvc_recv Recovering; aux_restart rep_rec_number
-// rep_rec_recv (never written under these cfgs: the lowering stores none of them); step_action.  Refused as above: primes, UNCHANGED, temporal operators.  A
-// whole log as a value (m.log = rep_log[r]) is refused: compare lengths and entries.
+// rep_rec_recv (never written under these cfgs: the lowering stores none of them); step_action (by the state entry: it belongs to step predicates, below).
+// Refused as above by the state entry: primes, UNCHANGED, temporal operators.  A whole log as a value (m.log = rep_log[r]) is refused: compare lengths and entries.
 // WHERE THIS DEPARTS FROM TLC, beyond the list above (whose conventions hold: an absent entry reads 0 and its operation equals Nil, an absent field reads 0,
 // an index out of range yields -1, \div by zero gives 0):
 //   * Len(m.log) is the number of entries the message carries.  For a NewStateMsg m.log is a function on first_op..op_number, not a sequence, and TLA+ gives
@@ -82,6 +82,24 @@
 //                print them (TimerSendSVC ReceiveHigherSVC ReceiveMatchingSVC SendDVC ReceiveHigherDVC ReceiveMatchingDVC SendSV ReceiveSV
 //                ReceiveClientRequest ReceivePrepareMsg ReceivePrepareOkMsg ExecuteOp SendGetState ReceiveGetState ReceiveNewState).  TLA+ cannot name the
 //                disjunct of a step; a property that needs it there restates the action's guard.
+// STEP PREDICATES ON THE ANALYSIS MODELS (where_compile(.., step = true) with a model of VR_STATE_TRANSFER.tla or VR_APP_STATE.tla; vsrmc_step_predicates_compile):
+// the step language above over the analysis models' variable table.
+//   prime        after any state variable of the table and after a primary expression: rep_status'[r] .. rep_sent_sv'[r], no_progress'[r], no_progress_ctr',
+//                rep_peer_op_number'[r][p], aux_svc', aux_client_acked'[v]; the logs rep_log'[r] and, on VR_APP_STATE.tla, rep_app_state'[r] wherever a log s may
+//                stand (Len(s), DOMAIN s, s[i], s[i].operation); \A m \in DOMAIN messages', messages'[m], and m.log of a message bound over either bag (of the
+//                bag it was bound over).  VR_APP_STATE.tla: Cardinality(rep_recv_dvc[r])' / Cardinality(rep_recv_dvc'[r]), \A / \E d \in rep_recv_dvc'[r]; the
+//                fields and d.log of such a d are the successor's whatever the context, those of a d bound over rep_recv_dvc[r] the state's.  The rules
+//                above carry over: no double prime, no prime over a prime (a bound variable cannot be primed), at most two nested message quantifiers in
+//                any mix of bags, no message of one bag as a key of the other.
+//   UNCHANGED e  for anything = compares; for a log of a replica, rep_log[r] or rep_app_state[r]: Len and the three positions are compared (still not a whole-log
+//                value: rep_log'[r] = rep_log[r] is refused); for the whole per-replica variables rep_status, rep_view_number, rep_op_number,
+//                rep_commit_number, rep_last_normal_view, rep_log, no_progress and, on VR_APP_STATE.tla, rep_app_state, unfolded over replicas.  UNCHANGED messages
+//                (a bag is not a value) and UNCHANGED rep_recv_dvc (compare Cardinality, or quantify over both sets) are refused with that reason; UNCHANGED of
+//                another whole variable names the list.
+//   step_action  against the fifteen names of the action table (vsr_model.hpp: action_name; the three specs name their Next disjuncts alike).
+// Refusals keep the "line:col: reason" form and name the model where the state language's do.  A text without primes compiles to exactly the ops
+// vsrmc_predicates_compile gives it.  vsrmc_step_compile keeps refusing these models ("step predicates: VSR.tla only").
+//
 // Everything else keeps its meaning on both sides of a pair, the defined results of out-of-domain accesses included.  A pair whose successor equals its
 // state is evaluated like any other (TLC's [][P]_vars would skip a stuttering step).  A text without primes compiles to exactly the ops the state entry
 // gives it; the state entry (step = false) keeps refusing primes, UNCHANGED and step_action.  Still out of scope: temporal operators, fairness, ENABLED,
@@ -338,6 +356,7 @@ struct Parser {
 };
 
 // kind 0: integer constant, 1: value constant (index + 1), 2: message loop v (primed: over messages'), 3: a held DoViewChange, v = replica << 4 | source slot
+// (primed: of rep_recv_dvc'[r] — its fields are read in the successor whatever the context)
 struct Binding { std::string name; int kind; int v; bool primed = false; };
 struct Def { NodeP body; };
 
@@ -484,6 +503,12 @@ struct Compiler {
     }
     return root;
   }
+  static bool has_prime(const NodeP& n) {
+    if (n->k == N_PRIME || n->k == N_UNCHANGED) return true;
+    for (const NodeP& c : n->c)
+      if (has_prime(c)) return true;
+    return false;
+  }
   int entry_field(const NodeP& at, const std::string& f) {
     if (AN) {                                                   // the entry is already its value + 1
       if (f == "operation") return TY_VALUE;
@@ -524,22 +549,26 @@ struct Compiler {
     if (s == "Recovering") fail(at, std::string("Recovering is not a status of ") + Y.spec + " (Normal, ViewChange, StateTransfer)");
     if (s == "aux_restart" || s == "rep_rec_number" || s == "rep_rec_recv" || s == "RecoveryMsg" || s == "RecoveryResponseMsg")
       fail(at, s + " is never written under the cfg of " + Y.spec + ": the lowering does not store it");
-    if (s == "step_action") fail(at, std::string("step_action belongs to step predicates, which are not built for ") + Y.spec);
+    if (s == "step_action" && !step) fail(at, std::string("step_action belongs to step predicates, which are not built for ") + Y.spec);
   }
   // a sequence of entries: 1 rep_log[r], 2 rep_app_state[r], 3 m.log of a bound message, 4 d.log of a held DoViewChange
-  struct Seq { int kind = 0; NodeP r; int loop = 0, dr = 0, ds = 0; };
+  // lp: the sequence is the successor's (rep_log'[r], or the context is primed; d.log of a d bound over rep_recv_dvc'[r]); m.log is the loop's bag word
+  struct Seq { int kind = 0; NodeP r; int loop = 0, dr = 0, ds = 0; bool lp = false; };
   bool seq_of(const NodeP& n, Seq* q) const {
     std::vector<Acc> acc;
+    bool pr = false;
     NodeP root = flatten(n, acc);
+    if (root->k == N_PRIME && root->c[0]->k == N_ID && (root->c[0]->s == "rep_log" || (Y.app_state && root->c[0]->s == "rep_app_state"))) root = strip_prime(root, &pr);
     if (root->k != N_ID || acc.size() != 1) return false;
     if (const Binding* b = lookup(root->s)) {
       if (!acc[0].field || acc[0].name != "log") return false;
       if (b->kind == 2) { q->kind = 3; q->loop = b->v; return true; }
-      if (b->kind == 3) { q->kind = 4; q->dr = b->v >> 4; q->ds = b->v & 15; return true; }
+      if (b->kind == 3) { q->kind = 4; q->dr = b->v >> 4; q->ds = b->v & 15; q->lp = b->primed; return true; }
       return false;
     }
     if (acc[0].field || defs.count(root->s)) return false;
     q->r = acc[0].ix;
+    q->lp = P || pr;
     if (root->s == "rep_log") { q->kind = 1; return true; }
     if (Y.app_state && root->s == "rep_app_state") { q->kind = 2; return true; }
     return false;
@@ -549,10 +578,10 @@ struct Compiler {
   void seq_len(const Seq& q) {
     std::vector<int> vals;
     switch (q.kind) {
-      case 1: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift, Y.log_width); emit(W_BLOGLEN, 0, 0); }, false); break;
-      case 2: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), 7, 2); }, false); break;   // Len(rep_app_state[r]) = rep_commit_number[r]
+      case 1: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift, Y.log_width); emit(W_BLOGLEN, 0, 0); }, q.lp); break;
+      case 2: indexed({Ix{q.r, 1, M.R, TY_INT}}, 0, vals, -1, [&](const std::vector<int>& v) { ldbits(aword(v[0]), 7, 2); }, q.lp); break;   // Len(rep_app_state[r]) = rep_commit_number[r]
       case 3: emit(W_MLOGLEN, (u32)q.loop, +1); break;
-      case 4: ldbits(bword(q.dr), dvc_shift(q.ds) + 8, 9); emit(W_BLOGLEN, 0, 0); break;
+      case 4: indexed({}, 0, vals, 0, [&](const std::vector<int>&) { ldbits(bword(q.dr), dvc_shift(q.ds) + 8, 9); emit(W_BLOGLEN, 0, 0); }, q.lp); break;
     }
   }
   // entry i of the sequence in the one form every entry is compared in (value + 1, 0 = absent: outside the domain, or a replica out of range)
@@ -561,15 +590,16 @@ struct Compiler {
     switch (q.kind) {
       case 1:
         indexed({Ix{q.r, 1, M.R, TY_INT}, Ix{i, 1, 3, TY_INT}}, 0, vals, 0,
-                [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift + 3 * (v[1] - 1), 3); emit(W_ENTN, 0, 0); }, false);
+                [&](const std::vector<int>& v) { ldbits(aword(v[0]) + Y.log_word, Y.log_shift + 3 * (v[1] - 1), 3); emit(W_ENTN, 0, 0); }, q.lp);
         break;
       case 2:
-        indexed({Ix{q.r, 1, M.R, TY_INT}, Ix{i, 1, 3, TY_INT}}, 0, vals, 0, [&](const std::vector<int>& v) { emit(W_APPENT, (u32)aword(v[0]) | ((u32)v[1] << 8), +1); }, false);
+        indexed({Ix{q.r, 1, M.R, TY_INT}, Ix{i, 1, 3, TY_INT}}, 0, vals, 0,
+                [&](const std::vector<int>& v) { emit(W_APPENT, (u32)aword(v[0]) | ((u32)v[1] << 8) | ((u32)P << 20), +1); }, q.lp);
         break;
       case 3: indexed({Ix{i, 1, 3, TY_INT}}, 0, vals, 0, [&](const std::vector<int>& v) { emit(W_MLOGENT, (u32)q.loop | ((u32)v[0] << 1), +1); }, false); break;
       case 4:
         indexed({Ix{i, 1, 3, TY_INT}}, 0, vals, 0,
-                [&](const std::vector<int>& v) { ldbits(bword(q.dr), dvc_shift(q.ds) + 8 + 3 * (v[0] - 1), 3); emit(W_ENTN, 0, 0); }, false);
+                [&](const std::vector<int>& v) { ldbits(bword(q.dr), dvc_shift(q.ds) + 8 + 3 * (v[0] - 1), 3); emit(W_ENTN, 0, 0); }, q.lp);
         break;
     }
   }
@@ -582,12 +612,13 @@ struct Compiler {
     return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
   }
   // \A / \E d \in rep_recv_dvc[r]: unfolded over the source slots, each guarded by its present bit; a replica that is not a constant unfolds over replicas too
-  void quant_dvc(const NodeP& n, size_t var, const NodeP& r) {
+  // lp: the set is the successor's (rep_recv_dvc'[r], or the context is primed)
+  void quant_dvc(const NodeP& n, size_t var, const NodeP& r, bool lp) {
     const bool forall = n->s == "A";
     auto slots = [&](int rv) {
       for (int s = 1; s <= M.R; s++) {
-        ldbits(bword(rv), dvc_shift(s), 1);
-        env.push_back(Binding{n->vars[var], 3, (rv << 4) | s});
+        { const bool saved = P; P = lp; ldbits(bword(rv), dvc_shift(s), 1); P = saved; }
+        env.push_back(Binding{n->vars[var], 3, (rv << 4) | s, lp});
         compile_quant(n, var + 1);
         env.pop_back();
         bin(forall ? W_IMP : W_AND);
@@ -613,6 +644,8 @@ struct Compiler {
     std::vector<Acc> acc;
     bool root_primed = false;
     NodeP root = strip_prime(flatten(n, acc), &root_primed);
+    if (root->k == N_PRIME && root->c[0]->k == N_ID && lookup(root->c[0]->s)) fail(root, root->c[0]->s + " is a bound variable: it cannot be primed");
+    if (root->k == N_PRIME && has_prime(root->c[0])) fail(root, "double prime: a primed expression that is indexed is primed again");
     if (root->k != N_ID) fail(n, "only state variables and bound messages can be indexed or have fields");
     const bool lp = P || root_primed;
     const std::string& s = root->s;
@@ -629,15 +662,20 @@ struct Compiler {
         const int dr = b->v >> 4, ds = b->v & 15;
         if (!acc[0].field) fail(acc[0].at, "a message cannot be indexed");
         const std::string& f = acc[0].name;
-        if (f == "log") { Seq q; q.kind = 4; q.dr = dr; q.ds = ds; return compile_log_path(n, acc, q); }
+        if (f == "log") { Seq q; q.kind = 4; q.dr = dr; q.ds = ds; q.lp = b->primed; return compile_log_path(n, acc, q); }
         if (acc.size() != 1) fail(n, s + "." + f + " has no fields and cannot be indexed");
         if (f == "type") { push(T_DVC); return TY_MTYPE; }
-        if (f == "view_number") { ldbits(bword(dr), 0, 3); return TY_INT; }
         if (f == "source") { push(ds); return TY_INT; }
         if (f == "dest") { push(dr); return TY_INT; }
-        if (f == "last_normal_vn") { ldbits(bword(dr), dvc_shift(ds) + 1, 3); return TY_INT; }
-        if (f == "op_number") { ldbits(bword(dr), dvc_shift(ds) + 4, 2); return TY_INT; }
-        if (f == "commit_number") { ldbits(bword(dr), dvc_shift(ds) + 6, 2); return TY_INT; }
+        static const struct { const char* name; int shift, width; } DF[] = {{"view_number", -1, 3}, {"last_normal_vn", 1, 3}, {"op_number", 4, 2}, {"commit_number", 6, 2}};
+        for (const auto& e : DF)
+          if (f == e.name) {                                    // of the side d was bound on, whatever the context
+            const bool saved = P;
+            P = b->primed;
+            ldbits(bword(dr), e.shift < 0 ? 0 : dvc_shift(ds) + e.shift, e.width);
+            P = saved;
+            return TY_INT;
+          }
         fail(acc[0].at, "a DoViewChangeMsg has no field " + f);
       }
       if (b->kind != 2) fail(n, s + " is not a message: it has no fields and cannot be indexed");
@@ -699,6 +737,7 @@ struct Compiler {
       Seq q;
       q.kind = s == "rep_log" ? 1 : 2;
       q.r = acc[0].ix;
+      q.lp = lp;
       seq_entry(q, acc[1].ix);
       return acc.size() == 3 ? entry_field(acc[2].at, acc[2].name) : TY_ENTRY;
     }
@@ -779,9 +818,13 @@ struct Compiler {
       }
       return TY_BOOL;
     }
-    if (Y.app_state && set->k == N_INDEX && set->c[0]->k == N_ID && set->c[0]->s == "rep_recv_dvc" && !lookup("rep_recv_dvc") && !defs.count("rep_recv_dvc")) {
-      quant_dvc(n, var, set->c[1]);
-      return TY_BOOL;
+    if (Y.app_state && set->k == N_INDEX && !lookup("rep_recv_dvc") && !defs.count("rep_recv_dvc")) {
+      bool hp = false;
+      const NodeP held = strip_prime(set->c[0], &hp);           // rep_recv_dvc'[r]: the successor's set
+      if (held->k == N_ID && held->s == "rep_recv_dvc") {
+        quant_dvc(n, var, set->c[1], P || hp);
+        return TY_BOOL;
+      }
     }
     if (set->k == N_DOMAIN && (logr = log_of(set->c[0], &loglp))) {    // 1..Len(rep_log[r]): unfolded over the three positions, each guarded by its presence
       for (int k = 1; k <= 3; k++) {
@@ -822,10 +865,77 @@ struct Compiler {
     fail(set, "a quantifier ranges over replicas, clients, Values, a..b, DOMAIN rep_log[r] or DOMAIN messages");
   }
 
+  NodeP num_node(const NodeP& at, int v) const {
+    NodeP kn = std::make_shared<Node>();
+    kn->k = N_NUM; kn->v = v; kn->line = at->line; kn->col = at->col;
+    return kn;
+  }
+  // Len(s)' = Len(s) /\ s'[i] = s[i] for the three positions (an absent entry equals an absent entry)
+  void unchanged_seq(Seq q) {
+    q.lp = true;
+    seq_len(q);
+    q.lp = false;
+    seq_len(q);
+    bin(W_EQ);
+    for (int i = 1; i <= 3; i++) {
+      const NodeP in = num_node(q.r, i);
+      q.lp = true;
+      seq_entry(q, in);
+      q.lp = false;
+      seq_entry(q, in);
+      bin(W_EQ);
+      bin(W_AND);
+    }
+  }
   // UNCHANGED e == (e' = e).  A whole per-replica variable unfolds over replicas.
   int compile_unchanged(const NodeP& n) {
     const NodeP& e = n->c[0];
     if (P) fail(n, "UNCHANGED inside a primed expression (it contains a prime itself)");
+    if (AN) {                                                     // the analysis models: their own words and logs
+      if (e->k == N_ID && !lookup(e->s) && !defs.count(e->s)) {
+        refuse_absent(e, e->s);
+        if (e->s == "messages")
+          fail(e, "UNCHANGED messages: a whole bag is not a value that can be compared; quantify over DOMAIN messages and DOMAIN messages' instead");
+        if (Y.app_state && e->s == "rep_recv_dvc")
+          fail(e, std::string("UNCHANGED rep_recv_dvc: the sets of held DoViewChanges of ") + Y.spec +
+                  " are not values that can be compared; compare Cardinality(rep_recv_dvc[r]) or quantify over rep_recv_dvc[r] and rep_recv_dvc'[r]");
+        const struct { const char* name; int shift, width; } V[] = {{"rep_status", 0, 2}, {"rep_view_number", 2, 3}, {"rep_op_number", 5, 2}, {"rep_commit_number", 7, 2},
+                                                                    {"rep_last_normal_view", 9, 3}, {"no_progress", Y.noprog_shift, 1}};
+        for (const auto& v : V)
+          if (e->s == v.name) {
+            for (int r = 1; r <= M.R; r++) {
+              P = true;
+              ldbits(aword(r), v.shift, v.width);
+              P = false;
+              ldbits(aword(r), v.shift, v.width);
+              bin(W_EQ);
+              if (r > 1) bin(W_AND);
+            }
+            return TY_BOOL;
+          }
+        if (e->s == "rep_log" || (Y.app_state && e->s == "rep_app_state")) {
+          for (int r = 1; r <= M.R; r++) {
+            Seq q;
+            q.kind = e->s == "rep_log" ? 1 : 2;
+            q.r = num_node(e, r);
+            unchanged_seq(q);
+            if (r > 1) bin(W_AND);
+          }
+          return TY_BOOL;
+        }
+        static const char* const OTHER[] = {"rep_sent_dvc", "rep_sent_sv", "rep_peer_op_number", "aux_client_acked"};
+        for (const char* o : OTHER)
+          if (e->s == o)
+            fail(e, "UNCHANGED " + e->s + ": a whole variable of " + Y.spec + " can be rep_status, rep_view_number, rep_op_number, rep_commit_number, rep_last_normal_view, rep_log, no_progress" +
+                    (Y.app_state ? " or rep_app_state" : "") + "; apply UNCHANGED to an element otherwise");
+      }
+      Seq q;
+      if (seq_of(e, &q) && (q.kind == 1 || q.kind == 2)) {        // UNCHANGED rep_log[r] / rep_app_state[r]: length and positions, still not a whole-log value
+        if (q.lp) fail(e, "double prime: UNCHANGED of a primed log");
+        unchanged_seq(q);
+        return TY_BOOL;
+      }
+    }
     if (e->k == N_ID && !lookup(e->s) && !defs.count(e->s)) {
       static const struct { const char* name; int word, shift, width; } V[] = {{"rep_status", 0, 0, 2}, {"rep_view_number", 0, 2, 3}, {"rep_op_number", 0, 5, 2},
                                                                                  {"rep_commit_number", 0, 7, 2}, {"rep_last_normal_view", 0, 9, 3}, {"rep_log", 1, 0, 24}};
@@ -879,6 +989,8 @@ struct Compiler {
                                            "rep_peer_op_number", "rep_client_table", "rep_log", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};
           for (const char* e : FN)
             if (n->c[0]->s == e) fail(n, n->c[0]->s + "' is a function: apply it to an index");
+          if (AN && (n->c[0]->s == "no_progress" || (Y.app_state && (n->c[0]->s == "rep_app_state" || n->c[0]->s == "rep_recv_dvc"))))
+            fail(n, n->c[0]->s + "' is a function: apply it to an index");
         }
         P = true;
         const int t = compile(n->c[0]);
@@ -896,7 +1008,9 @@ struct Compiler {
         if (AN) {
           Seq q;
           std::vector<Acc> acc;
+          bool rp = false;
           NodeP root = flatten(a, acc);
+          if (root->k == N_PRIME && root->c[0]->k == N_ID && root->c[0]->s == "rep_recv_dvc") root = strip_prime(root, &rp);
           if (n->s == "Len") {
             if (seq_of(a, &q)) { seq_len(q); return TY_INT; }
           } else if (Y.app_state && root->k == N_ID && root->s == "rep_recv_dvc" && !lookup(root->s) && !defs.count(root->s) && acc.size() == 1 && !acc[0].field) {
@@ -906,7 +1020,7 @@ struct Compiler {
                 ldbits(bword(r[0]), dvc_shift(s), 1);
                 if (s > 1) bin(W_ADD);
               }
-            }, false);
+            }, P || rp);
             return TY_INT;
           }
           if (a->k == N_INDEX || a->k == N_FIELD || a->k == N_ID) compile(a);   // (an unknown or refused name says so itself)
@@ -981,11 +1095,8 @@ struct Compiler {
         if (s == "aux_svc") { ldbits(0, 8, 3); return TY_INT; }
         if (step) {                                             // not TLA+: the Next disjunct that produced the pair, and the names traces print
           if (s == "step_action") { emit(W_STEPACT, 0, +1); return TY_ACTION; }
-          static const char* const ACT[] = {"TimerSendSVC", "ReceiveHigherSVC", "ReceiveMatchingSVC", "SendDVC", "ReceiveHigherDVC", "ReceiveMatchingDVC", "SendSV",
-                                            "ReceiveSV", "ReceiveClientRequest", "ReceivePrepareMsg", "ReceivePrepareOkMsg", "ExecuteOp", "SendGetState", "ReceiveGetState",
-                                            "ReceiveNewState"};
-          for (int a = 0; a < 15; a++)
-            if (s == ACT[a]) { push(a + 1); return TY_ACTION; }
+          for (int a = 1; a < (int)A_COUNT; a++)                 // the action table's own names (vsr_model.hpp): the three specs name their disjuncts alike
+            if (s == action_name(a)) { push(a); return TY_ACTION; }
         }
         static const char* const STATE[] = {"rep_status", "rep_view_number", "rep_op_number", "rep_commit_number", "rep_last_normal_view", "rep_sent_dvc", "rep_sent_sv",
                                             "rep_peer_op_number", "rep_client_table", "rep_log", "rep_svc_recv", "rep_dvc_recv", "aux_client_acked", "messages"};

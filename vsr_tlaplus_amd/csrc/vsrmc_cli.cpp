@@ -43,7 +43,8 @@ static void usage() {
       "  -invariant NAME[,NAME]  the same scan for ~NAME: a state in which NAME is false is reported like a violation of a built-in invariant (exit 12)\n"
       "  -whereReport      count the states that satisfy each exported predicate, level by level, without stopping; with -json a \"where\" object in\n"
       "                    the level lines.  Levels that are never stored (the Virtual / Probe lines) are not examined, and the report says how many\n"
-      "  -steps FILE       step predicates (the same language plus primed variables, UNCHANGED and step_action; an example: tools/steps_example.txt), evaluated\n"
+      "  -steps FILE       step predicates (the same language plus primed variables, UNCHANGED and step_action, for any loaded cfg; examples: tools/steps_example.txt,\n"
+      "                    tools/steps_model2_example.txt, tools/steps_model3_example.txt), evaluated\n"
       "                    on every transition out of every stored level (a file of its own: -predicates FILE goes through the state compiler).  Used by:\n"
       "  -stepInvariant NAME[,NAME]  a transition on which NAME is false ends the run: \"Error: Action property NAME is violated.\", the behaviour with\n"
       "                    that step at its end and the step's action name (exit 12; -dumpTrace tla FILE writes it, -json adds a line)\n"
@@ -322,7 +323,7 @@ int main(int argc, char** argv) {
     std::stringstream pss;
     pss << pf.rdbuf();
     const std::string text = pss.str();
-    if (vsrmc_step_compile(m, text.c_str(), &s_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", steps_file.c_str(), vsrmc_last_error()); return 1; }
+    if (vsrmc_step_predicates_compile(m, text.c_str(), &s_all) != 0) { std::fprintf(stderr, "Error: %s:%s\n", steps_file.c_str(), vsrmc_last_error()); return 1; }
     vsrmc_where_desc wd;
     vsrmc_where_describe(s_all, &wd);
     for (int k = 0; k < wd.n_names; k++) step_names.push_back(wd.names[k]);
@@ -337,7 +338,7 @@ int main(int argc, char** argv) {
         if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", steps_file.c_str(), step_query_names[k].c_str()); return 2; }
         local += "\nQuery" + std::to_string(k) + " == " + (k < n_step_reach ? "" : "~") + step_query_names[k];
       }
-      if (vsrmc_step_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+      if (vsrmc_step_predicates_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
   }
   if (!reach_arg.empty() || !invariant_arg.empty() || where_report) {
