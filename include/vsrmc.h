@@ -511,6 +511,44 @@ typedef struct vsrmc_sim_result {
 int32_t vsrmc_simulate(const vsrmc_model* m, int32_t device, uint32_t n_walkers, int32_t max_depth, uint64_t seed,
                        double max_seconds, vsrmc_sim_result* out);
 
+/* ---- simulation mode with the user's own predicates on every walk (csrc/vsr_sim_where.hpp: k_simulate_where) ----------------------
+ * The state predicates (vsrmc_predicates_compile) and step predicates (vsrmc_step_predicates_compile) of the sections above, evaluated on random walks
+ * instead of stored BFS levels: walks reach the depths no level is ever stored at.  Either program may be NULL, not both.  vsrmc_simulate is unchanged.
+ * THE ITERATION CONTRACT.  A launch ("round") is 64 iterations of every walker.  In one iteration a walker does exactly one of two things:
+ *   start  it has no walk yet, or its depth equals max_depth, or its state has no enabled instance: it puts Init into its record.  The state program
+ *          is evaluated on Init.  No random draw is taken.
+ *   step   one draw of the walker's generator (xorshift64*: x ^= x >> 12; x ^= x << 25; x ^= x >> 27; draw = x * 0x2545F4914F6CDD1D; walker i's
+ *          initial x is the i-th output of the splitmix64 stream that starts at `seed`, 1 if that is 0 — exactly vsrmc_simulate's); pick = draw % total
+ *          over the enabled (action, binding) instances in ordinal order; the instance is generated; the STEP program is evaluated on the pair (state,
+ *          successor) BEFORE the walker moves; the walker moves; the STATE program is evaluated on the state it now stands on; the built-in invariants
+ *          are checked as in vsrmc_simulate.
+ *   Without a stop every walker evaluates one state per iteration: n_states == steps + walks == 64 * rounds * n_walkers, and n_pairs == steps.
+ * count_state[k] / count_step[k]: the states / pairs that satisfy exported predicate k of the state / step program — exact.
+ * stop = 1: the run ends at the first state or pair with any bit set, or the first violated built-in invariant; found says which (of several in one
+ *   iteration of one walker: the step program, then the state program, then the invariants), viol_mask the bits, ords[0 .. viol_steps) the walk — for
+ *   found = 4 it INCLUDES the offending step; found = 3 with viol_steps == 0: Init itself satisfies the predicate.  vsrmc_model_replay gives the states.
+ *   The counts are then those of the rounds up to and including the one that stopped (other walkers were cut short in it).
+ * stop = 0: count only (the report mode); the built-in invariants are not a stop reason.  An evaluation / representation error on a walk ends
+ *   the run in either mode (found = 2).
+ * max_rounds > 0: the run ends after exactly that many launches and the clock is not consulted — every count is then the same in every run with the same
+ *   seed, each walker's path depending on its own generator only.  max_rounds = 0: launches until max_seconds have passed, as vsrmc_simulate.
+ * Refused with VSRMC_E_ARG before any device is looked at: both programs NULL; a step program as state_prog or a state program as step_prog; a program
+ * "compiled for another model"; max_depth outside 1..512.
+ * Where this departs from the stored-level scans: a walk has no VIEW representative — the aux variables a state program reads are the walk's own. */
+typedef struct vsrmc_sim_where_result {
+  int32_t found;            /* 0 none, 1 built-in invariant, 2 error, 3 state predicate, 4 step predicate */
+  int32_t viol_mask;        /* found 1/2: as vsrmc_sim_result; found 3/4: the predicate bits of the hit */
+  int32_t viol_steps;
+  uint64_t steps, walks, rounds;
+  uint64_t n_states, n_pairs;              /* evaluations of each program */
+  uint64_t count_state[8], count_step[8];
+  double seconds;
+  uint32_t ords[512];
+} vsrmc_sim_where_result;
+int32_t vsrmc_simulate_where(const vsrmc_model* m, int32_t device, const vsrmc_where* state_prog, const vsrmc_where* step_prog,
+                             int32_t stop, uint32_t n_walkers, int32_t max_depth, uint64_t seed,
+                             double max_seconds, uint64_t max_rounds, vsrmc_sim_where_result* out);
+
 /* ---- sharded seen-set (≙ tlc2.tool.fp.MultiFPSet across GPUs): the phases of one BFS level -----------------------
  * world ranks, one per GPU; owner(fp) = ((fp >> 40) & 0xFFFFFF) % world.  The caller (vsr_tlaplus_amd/sharded.py over
  * torch.distributed / RCCL) owns the exchange buffers and moves them between ranks; every pointer is a device pointer.

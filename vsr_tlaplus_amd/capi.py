@@ -82,6 +82,12 @@ class SimResult(C.Structure):
                 ("steps", C.c_uint64), ("walks", C.c_uint64), ("seconds", C.c_double), ("ords", C.c_uint32 * 512)]
 
 
+class SimWhereResult(C.Structure):
+    _fields_ = [("found", C.c_int32), ("viol_mask", C.c_int32), ("viol_steps", C.c_int32), ("steps", C.c_uint64), ("walks", C.c_uint64),
+                ("rounds", C.c_uint64), ("n_states", C.c_uint64), ("n_pairs", C.c_uint64), ("count_state", C.c_uint64 * 8),
+                ("count_step", C.c_uint64 * 8), ("seconds", C.c_double), ("ords", C.c_uint32 * 512)]
+
+
 # every symbol include/vsrmc.h declares: name -> (restype, argtypes)
 V = C.c_void_p
 SYMBOLS = {
@@ -155,6 +161,8 @@ SYMBOLS = {
     "vsrmc_queue_size": (C.c_int32, [V, C.POINTER(C.c_uint64)]),
     "vsrmc_queue_destroy": (None, [V]),
     "vsrmc_simulate": (C.c_int32, [V, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.c_double, C.POINTER(SimResult)]),
+    "vsrmc_simulate_where": (C.c_int32, [V, C.c_int32, V, V, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.c_double, C.c_uint64,
+                                         C.POINTER(SimWhereResult)]),
     "vsrmc_checker_probe": (C.c_int32, [V, C.POINTER(LevelInfo)]),
     "vsrmc_checker_probe2": (C.c_int32, [V, C.POINTER(LevelInfo), C.POINTER(LevelInfo)]),
     "vsrmc_checker_probe3": (C.c_int32, [V, C.POINTER(LevelInfo), C.POINTER(LevelInfo), C.POINTER(LevelInfo)]),

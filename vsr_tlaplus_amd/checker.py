@@ -253,6 +253,30 @@ class Model:
             out["trace"] = self.replay(ords, device)
         return out
 
+    def simulate_where(self, state=None, step=None, stop=True, n_walkers=1 << 16, max_depth=100, seed=1, max_seconds=10.0, max_rounds=0, device=0):
+        """Random walks with the user's own predicates on every walk (k_simulate_where; the iteration contract: include/vsrmc.h).  `state`: a Where of
+        compile_predicates, evaluated on every state a walker stands on; `step`: a Where of compile_step_predicates, on every pair it takes; one may be
+        None.  stop=True ends the run at the first state / pair with any bit set (found 3 / 4) or violated built-in invariant (found 1); stop=False only
+        counts.  max_rounds > 0: exactly that many launches of 64 iterations per walker, every count the same in every run with the same seed.
+        -> dict(found, viol_mask, viol_steps, steps, walks, rounds, n_states, n_pairs, seconds, state_names, step_names, count_state={name: n},
+        count_step={name: n}, hit=[names of the bits of viol_mask] for found 3 / 4, ordinals and trace=[(action name, wire record)] for found 1, 3, 4:
+        for found 4 the last step of the trace is the pair that was hit)."""
+        r = capi.SimWhereResult()
+        check(capi.load().vsrmc_simulate_where(self._h, device, state._h if state is not None else None, step._h if step is not None else None,
+                                               int(bool(stop)), n_walkers, max_depth, C.c_uint64(int(seed) & (2 ** 64 - 1)), max_seconds, max_rounds,
+                                               C.byref(r)))
+        sn = list(state.names) if state is not None else []
+        pn = list(step.names) if step is not None else []
+        out = dict(found=r.found, viol_mask=r.viol_mask, viol_steps=r.viol_steps, steps=r.steps, walks=r.walks, rounds=r.rounds, n_states=r.n_states,
+                   n_pairs=r.n_pairs, seconds=r.seconds, state_names=sn, step_names=pn, count_state={nm: int(r.count_state[k]) for k, nm in enumerate(sn)},
+                   count_step={nm: int(r.count_step[k]) for k, nm in enumerate(pn)}, hit=None, ordinals=None, trace=None)
+        if r.found in (3, 4):
+            out["hit"] = [nm for k, nm in enumerate(sn if r.found == 3 else pn) if (r.viol_mask >> k) & 1]
+        if r.found in (1, 3, 4):
+            out["ordinals"] = [int(r.ords[k]) for k in range(r.viol_steps)]
+            out["trace"] = self.replay(out["ordinals"], device)
+        return out
+
     def replay(self, ords, device=0):
         """Re-execute a path of ordinals from Init on the GPU -> [(action name, wire record)]."""
         n = len(ords)

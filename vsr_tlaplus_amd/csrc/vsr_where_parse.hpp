@@ -29,7 +29,8 @@
 //   * A model-value literal (v1) is refused when the model was loaded with SYMMETRY: values then enter only through bound variables, every predicate
 //     is symmetric, and a hit does not depend on which member of its orbit the search stored.
 //   * aux_svc and aux_client_acked are outside VIEW: of the states that differ only there the search keeps one representative (the smallest canonical
-//     auxkey), and a predicate on them sees that representative.
+//     auxkey), and a predicate on them sees that representative.  NOT SO ON A RANDOM WALK (vsr_sim_where.hpp): a walk has
+//     no VIEW representative; the aux variables a state program reads there are the walk's own — which is what TLC sees.
 //
 //   * (step predicates, below) the primed aux variables — aux_svc', aux_client_acked'[v] — are those of the successor AS THE ACTION GENERATES IT, before the
 //     search picks the representative of its VIEW class: a pair is (stored state, generated successor), not (stored state, stored state).

@@ -7,7 +7,7 @@
 // expanded (vsrmc_checker_terminal_scan) and the behaviour into the one with the smallest fingerprint is printed.  -terminalReport scans every
 // stored level without stopping.  -predicates FILE with -reach / -invariant / -whereReport evaluates the user's own state predicates (k_where) on every
 // stored level, where -checkDeadlock scans.  -steps FILE with -stepReach / -stepInvariant / -stepReport does the same for step predicates (primed variables:
-// csrc/vsr_step.hpp) over every transition out of every stored level.
+// csrc/vsr_step.hpp) over every transition out of every stored level.  With -simulate the same flags ask the same questions of random walks (csrc/vsr_sim_where.hpp).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +63,11 @@ static void usage() {
       "                    on through the seen-set alone (Virtual(L) / Probe(L+1) lines).  A seen-set that fills up is re-hashed into twice the\n"
       "                    slots while the device has the memory; when it cannot grow and is 85 %% full the run ends \"incomplete at depth N\" (exit 4).\n"
       "  -simulate         random walks instead of BFS (TLC -simulate): -depth N (default 100) -walkers N (131072) -seed S -maxSeconds T\n"
+      "                    With -predicates FILE -reach / -invariant and / or -steps FILE -stepReach / -stepInvariant the same questions are asked of every\n"
+      "                    state a walk stands on and every step it takes, at any depth (the BFS asks them of stored levels only): the first hit ends the\n"
+      "                    run with its behaviour; exit codes as above (12 violated, 0 reached, 14 not met).  With -whereReport / -stepReport the exported\n"
+      "                    predicates are counted over the walks instead, without stopping; -simRounds N: exactly N rounds of 64 steps per walker (the\n"
+      "                    counts are then the same in every run with the same seed) instead of -maxSeconds\n"
       "  -validateTrace F  read a TLC trace (trace expression, or console \"State k:\" form) and check on the GPU that it is a\n"
       "                    behaviour of the model: Init, then one generated successor after the other; reports the invariants\n"
       "                    its last state violates\n"
@@ -148,6 +153,7 @@ int main(int argc, char** argv) {
   unsigned sim_walkers = 1u << 17;
   unsigned long long sim_seed = 1;
   double sim_seconds = 60.0;
+  unsigned long long sim_rounds = 0;
   int max_depth = 1 << 30, device = 0, table_log2 = 0, probe2_at = 0, probe3_at = 0, host_mask = 0;   // 0 = sized from the free device memory
   double frontier_gib = 0.0, frontier_b_gib = 0.0;
   for (int i = 1; i < argc; i++) {
@@ -180,6 +186,7 @@ int main(int argc, char** argv) {
     else if (a == "-walkers" && i + 1 < argc) sim_walkers = (unsigned)std::strtoul(argv[++i], nullptr, 10);
     else if (a == "-seed" && i + 1 < argc) sim_seed = std::strtoull(argv[++i], nullptr, 10);
     else if (a == "-maxSeconds" && i + 1 < argc) sim_seconds = std::atof(argv[++i]);
+    else if (a == "-simRounds" && i + 1 < argc) sim_rounds = std::strtoull(argv[++i], nullptr, 10);
     else if (a == "-json") json = true;
     else if (a == "-coverage") coverage = true;
     else if (a == "-audit") audit = true;
@@ -243,45 +250,6 @@ int main(int argc, char** argv) {
       for (int b = 0; b < 5; b++)
         if (inv & (1 << b)) { std::printf("Its last state violates invariant %s.\n", names[b]); code = 12; }
     }
-    vsrmc_model_destroy(m);
-    return code;
-  }
-  if (simulate) {   // ≙ tlc2.TLC -simulate -depth N
-    vsrmc_sim_result r;
-    if (vsrmc_simulate(m, device, sim_walkers, sim_depth, sim_seed, sim_seconds, &r) != 0) {
-      std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
-      return 1;
-    }
-    std::printf("Running Random Simulation with seed %llu: %u walkers on the GPU, depth %d.\n", sim_seed, sim_walkers, sim_depth);
-    int code = 0;
-    if (r.found == 1) {
-      const char* const* names = INVARIANT_NAMES;
-      for (int b = 0; b < 5; b++)
-        if (r.viol_mask & (1 << b)) std::printf("Error: Invariant %s is violated.\n", names[b]);
-      std::printf("Error: The behavior up to this point is:\n");
-      uint64_t cap_w = (uint64_t)(r.viol_steps + 3) * 256, n_states = 0;
-      std::vector<uint64_t> words(cap_w), off(r.viol_steps + 3);
-      std::vector<int32_t> acts(r.viol_steps + 3);
-      if (vsrmc_model_replay(m, device, r.ords, r.viol_steps, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states) != 0) {
-        std::printf("Error: %s\n", vsrmc_last_error());
-        return 1;
-      }
-      for (uint64_t t = 0; t < n_states; t++) {
-        int64_t need = 0;
-        vsrmc_model_format_state(m, &words[off[t]], nullptr, 0, &need);
-        std::string buf((size_t)need, '\0');
-        vsrmc_model_format_state(m, &words[off[t]], &buf[0], need, &need);
-        std::printf("State %llu: <%s>\n%s\n\n", (unsigned long long)(t + 1), vsrmc_action_name(acts[t]), buf.c_str());
-      }
-      code = 12;
-    } else if (r.found == 2) {
-      std::printf("Error: a walk raised device error %d after %d steps.\n", r.viol_mask, r.viol_steps);
-      code = 1;
-    } else {
-      std::printf("Simulation stopped after %.1f s without a violation.\n", r.seconds);
-    }
-    std::printf("%llu states checked in %llu walks, %.3f s (%.3g steps/s).\n", (unsigned long long)r.steps, (unsigned long long)r.walks,
-                r.seconds, r.seconds > 0 ? (double)r.steps / r.seconds : 0.0);
     vsrmc_model_destroy(m);
     return code;
   }
@@ -365,6 +333,154 @@ int main(int argc, char** argv) {
       }
       if (vsrmc_predicates_compile(m, local.c_str(), &w_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
+  }
+  if (simulate) {   // ≙ tlc2.TLC -simulate -depth N
+    // the walk Init .. ords[n_steps), printed the way the BFS prints a behaviour
+    auto print_walk = [&](const char* header, const uint32_t* ords, int n_steps, std::vector<int32_t>* acts_out) -> bool {
+      std::printf("%s\n", header);
+      uint64_t cap_w = (uint64_t)(n_steps + 3) * 256, n_states = 0;
+      std::vector<uint64_t> words(cap_w), off(n_steps + 3);
+      std::vector<int32_t> acts(n_steps + 3);
+      if (vsrmc_model_replay(m, device, ords, n_steps, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states) != 0) {
+        std::printf("Error: %s\n", vsrmc_last_error());
+        return false;
+      }
+      for (uint64_t t = 0; t < n_states; t++) {
+        int64_t need = 0;
+        vsrmc_model_format_state(m, &words[off[t]], nullptr, 0, &need);
+        std::string buf((size_t)need, '\0');
+        vsrmc_model_format_state(m, &words[off[t]], &buf[0], need, &need);
+        std::printf("State %llu: <%s>\n%s\n\n", (unsigned long long)(t + 1), vsrmc_action_name(acts[t]), buf.c_str());
+      }
+      if (acts_out) acts_out->assign(acts.begin(), acts.begin() + n_states);
+      if (acts_out && !dump_trace_file.empty()) {
+        if (write_trace_expression(dump_trace_file, m, words, off, acts, n_states))
+          std::printf("The counter-example was written to %s (TLA+ trace expression).\n", dump_trace_file.c_str());
+        else
+          std::printf("Warning: cannot write %s\n", dump_trace_file.c_str());
+      }
+      return true;
+    };
+    auto destroy_all = [&]() {
+      if (w_all) vsrmc_where_destroy(w_all);
+      if (w_query) vsrmc_where_destroy(w_query);
+      if (s_all) vsrmc_where_destroy(s_all);
+      if (s_query) vsrmc_where_destroy(s_query);
+      vsrmc_model_destroy(m);
+    };
+    if (!w_all && !s_all) {                                         // no question of the user's: the built-in invariants alone (k_simulate)
+      if (!predicates_file.empty() || !steps_file.empty() || sim_rounds) {
+        std::fprintf(stderr, "Error: -simulate: -predicates FILE needs -reach / -invariant / -whereReport, -steps FILE needs -stepReach / -stepInvariant / -stepReport, "
+                             "-simRounds N needs one of them\n");
+        return 2;
+      }
+      vsrmc_sim_result r;
+      if (vsrmc_simulate(m, device, sim_walkers, sim_depth, sim_seed, sim_seconds, &r) != 0) {
+        std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+        return 1;
+      }
+      std::printf("Running Random Simulation with seed %llu: %u walkers on the GPU, depth %d.\n", sim_seed, sim_walkers, sim_depth);
+      int code = 0;
+      if (r.found == 1) {
+        const char* const* names = INVARIANT_NAMES;
+        for (int b = 0; b < 5; b++)
+          if (r.viol_mask & (1 << b)) std::printf("Error: Invariant %s is violated.\n", names[b]);
+        if (!print_walk("Error: The behavior up to this point is:", r.ords, r.viol_steps, nullptr)) return 1;
+        code = 12;
+      } else if (r.found == 2) {
+        std::printf("Error: a walk raised device error %d after %d steps.\n", r.viol_mask, r.viol_steps);
+        code = 1;
+      } else {
+        std::printf("Simulation stopped after %.1f s without a violation.\n", r.seconds);
+      }
+      std::printf("%llu states checked in %llu walks, %.3f s (%.3g steps/s).\n", (unsigned long long)r.steps, (unsigned long long)r.walks,
+                  r.seconds, r.seconds > 0 ? (double)r.steps / r.seconds : 0.0);
+      vsrmc_model_destroy(m);
+      return code;
+    }
+    // the user's predicates on every walk (k_simulate_where): first the report (count only), then the query (stop at the first hit)
+    std::printf("Running Random Simulation with seed %llu: %u walkers on the GPU, depth %d.\n", sim_seed, sim_walkers, sim_depth);
+    int code = 0;
+    vsrmc_sim_where_result r;
+    auto totals = [&]() {
+      std::printf("%llu states and %llu steps evaluated in %llu walks, %llu rounds, %.3f s (%.3g steps/s).\n", (unsigned long long)r.n_states, (unsigned long long)r.n_pairs,
+                  (unsigned long long)r.walks, (unsigned long long)r.rounds, r.seconds, r.seconds > 0 ? (double)r.steps / r.seconds : 0.0);
+    };
+    if (where_report || step_report) {
+      if (vsrmc_simulate_where(m, device, where_report ? w_all : nullptr, step_report ? s_all : nullptr, 0, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &r) != 0) {
+        std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+        return 1;
+      }
+      if (r.found == 2) {
+        std::printf("Error: a walk raised device error %d after %d steps.\n", r.viol_mask, r.viol_steps);
+        code = 1;
+      }
+      if (where_report)
+        for (size_t k = 0; k < where_names.size(); k++)
+          std::printf("Where report: %s holds in %llu of %llu states stood on by the walks.\n", where_names[k].c_str(), (unsigned long long)r.count_state[k],
+                      (unsigned long long)r.n_states);
+      if (step_report)
+        for (size_t k = 0; k < step_names.size(); k++)
+          std::printf("Step report: %s holds on %llu of %llu pairs taken by the walks.\n", step_names[k].c_str(), (unsigned long long)r.count_step[k],
+                      (unsigned long long)r.n_pairs);
+      if (json) {
+        std::string j = "{\"simulate\": true, \"rounds\": " + std::to_string((unsigned long long)r.rounds) + ", \"states\": " + std::to_string((unsigned long long)r.n_states) +
+                        ", \"pairs\": " + std::to_string((unsigned long long)r.n_pairs) + ", \"where\": {";
+        for (size_t k = 0; where_report && k < where_names.size(); k++) j += (k ? ", \"" : "\"") + where_names[k] + "\": " + std::to_string((unsigned long long)r.count_state[k]);
+        j += "}, \"steps\": {";
+        for (size_t k = 0; step_report && k < step_names.size(); k++) j += (k ? ", \"" : "\"") + step_names[k] + "\": " + std::to_string((unsigned long long)r.count_step[k]);
+        std::printf("%s}}\n", j.c_str());
+      }
+      totals();
+    }
+    if ((w_query || s_query) && code == 0) {
+      if (vsrmc_simulate_where(m, device, w_query, s_query, 1, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &r) != 0) {
+        std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+        return 1;
+      }
+      if (r.found == 3 || r.found == 4) {
+        // an invariant's (action property's) violation is reported before a reachability hit of the same state (pair), as the BFS does
+        const std::vector<std::string>& names = r.found == 3 ? query_names : step_query_names;
+        const size_t nr = r.found == 3 ? n_reach : n_step_reach;
+        int hit = -1;
+        for (size_t k = nr; k < names.size() && hit < 0; k++)
+          if (r.viol_mask & (1 << k)) hit = (int)k;
+        for (size_t k = 0; k < nr && hit < 0; k++)
+          if (r.viol_mask & (1 << k)) hit = (int)k;
+        if (hit < 0) { std::printf("Error: the walk that was reported has no bit of the query set.\n"); return 1; }
+        const bool inv = (size_t)hit >= nr;
+        const char* header = inv ? "Error: The behavior up to this point is:" : "The behavior up to this point is:";
+        if (inv) std::printf(r.found == 3 ? "Error: Invariant %s is violated.\n" : "Error: Action property %s is violated.\n", names[hit].c_str());
+        else std::printf(r.found == 3 ? "State satisfying %s found at depth %d by a random walk.\n" : "Step satisfying %s found by a random walk: the step out of depth %d.\n",
+                         names[hit].c_str(), r.found == 3 ? r.viol_steps + 1 : r.viol_steps);
+        std::vector<int32_t> acts;
+        if (!print_walk(header, r.ords, r.viol_steps, &acts)) return 1;
+        if (r.found == 4 && !acts.empty()) std::printf("The last step is %s of State %d.\n", vsrmc_action_name(acts.back()), r.viol_steps);
+        if (json)
+          std::printf("{\"simulate\": true, \"%s\": \"%s\", \"steps\": %d, \"action\": \"%s\"}\n",
+                      r.found == 3 ? (inv ? "invariant_violated" : "reached") : (inv ? "action_property_violated" : "step_reached"), names[hit].c_str(), r.viol_steps,
+                      acts.empty() ? "" : vsrmc_action_name(acts.back()));
+        code = inv ? 12 : 0;
+      } else if (r.found == 1) {
+        const char* const* names = INVARIANT_NAMES;
+        for (int b = 0; b < 5; b++)
+          if (r.viol_mask & (1 << b)) std::printf("Error: Invariant %s is violated.\n", names[b]);
+        std::vector<int32_t> acts;
+        if (!print_walk("Error: The behavior up to this point is:", r.ords, r.viol_steps, &acts)) return 1;
+        code = 12;
+      } else if (r.found == 2) {
+        std::printf("Error: a walk raised device error %d after %d steps.\n", r.viol_mask, r.viol_steps);
+        code = 1;
+      } else {
+        for (size_t k = 0; k < n_reach; k++) std::printf("No state satisfying %s was met by the walks.\n", query_names[k].c_str());
+        for (size_t k = 0; k < n_step_reach; k++) std::printf("No step satisfying %s was met by the walks.\n", step_query_names[k].c_str());
+        std::printf("Simulation stopped after %.1f s without a violation.\n", r.seconds);
+        if (n_reach || n_step_reach) code = 14;
+      }
+      totals();
+    }
+    destroy_all();
+    return code;
   }
   vsrmc_options o;
   vsrmc_options_default(&o);
