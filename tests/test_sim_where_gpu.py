@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import deep_predicates_reference as dp
 import sim_where_model as sm
 import step_models_reference as smr
 import step_reference as sr
@@ -92,10 +93,12 @@ def _assert_report_equals_model(r, want, state_preds, step_preds, n_walkers):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. exact counts against the model
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R, C, n, L, max_depth", [(3, 1, 2, 1, 12), (2, 1, 1, 1, 30)])
+@pytest.mark.parametrize("R, C, n, L, max_depth", [(3, 1, 2, 1, 12), (2, 1, 1, 1, 30), (5, 1, 2, 1, 40), (4, 1, 2, 1, 40)])
 def test_report_counts_equal_the_model(vt, R, C, n, L, max_depth):
     """100 walkers: the second wave has 36 walkers and 28 idle lanes, which must count nothing.  (2,1,1,1) has 76 states and its walks end in terminal
-    states at different times: lanes of one wave start and step in the same iteration."""
+    states at different times: lanes of one wave start and step in the same iteration.  At five and four replicas (replica blocks of four words, broadcasts
+    that append R - 1 bag entries to the walker's record in place) the walks run 40 steps deep, far enough to hold DoViewChanges, and a second pair of
+    programs — the R >= 4 sets of deep_predicates_reference.py — is counted over the same walks."""
     from oracle import pycodec, pyoracle as po
     m = vt.Model.from_constants(R=R, C_=C, n=n, L=L)
     PM = po.Model(R, C, tuple("v%d" % (i + 1) for i in range(n)), L)
@@ -111,6 +114,17 @@ def test_report_counts_equal_the_model(vt, R, C, n, L, max_depth):
     r2 = m.simulate_where(step=wp, stop=False, n_walkers=100, max_depth=max_depth, seed=11, max_rounds=1)
     assert r1["count_state"] == r["count_state"] and (r1["n_states"], r1["n_pairs"], r1["steps"], r1["walks"]) == (6400, 0, r["steps"], r["walks"])
     assert r2["count_step"] == r["count_step"] and (r2["n_states"], r2["n_pairs"], r2["steps"], r2["walks"]) == (0, r["steps"], r["steps"], r["walks"])
+    if R >= 4:
+        ws4, wp4 = m.compile_predicates(dp.text_of(dp.STATE)), m.compile_step_predicates(dp.text_of(dp.STEP))
+        want4 = _model_counts(vt, m, lambda words: pycodec.unpack(PM, words), dp.STATE, wr.bits_of, dp.STEP, sr.bits_of, 100, max_depth, 11, 64)
+        r4 = m.simulate_where(state=ws4, step=wp4, stop=False, n_walkers=100, max_depth=max_depth, seed=11, max_rounds=1)
+        _assert_report_equals_model(r4, want4, dp.STATE, dp.STEP, 100)
+        assert (want4["steps"], want4["walks"]) == (want["steps"], want["walks"]) and want["walks"] > 100      # the same walks; walkers start again at max_depth
+        held = want4["cs"][[p[0] for p in dp.STATE].index(dp.SIM_STATE_MUST_HIT)]
+        grew = want4["cp"][[p[0] for p in dp.STEP].index(dp.SIM_STEP_MUST_HIT)]
+        print("simulate_where (%d,%d,%d,%d): n_walkers 100, max_depth %d, seed 11, max_rounds 1; the model stands on %d states in which a DoViewChange is held "
+              "and takes %d pairs on which the held set grew" % (R, C, n, L, max_depth, held, grew))
+        assert held >= 1 and grew >= 1                                 # by the Python model, which does not run the kernel under test
 
 
 # ---------------------------------------------------------------------------------------------------------------------
