@@ -465,6 +465,67 @@ int32_t vsrmc_checker_probe_trace(vsrmc_checker* c, uint64_t* words, uint64_t ca
 int32_t vsrmc_checker_trace_to_violator(vsrmc_checker* c, uint64_t fp, uint64_t* words, uint64_t cap_words, uint64_t* off, int32_t* actions,
                                         uint64_t cap_states, uint64_t* n_states);
 
+/* ---- a user's predicates on the levels beyond the record buffers -----------------------------------------------------------------------
+ * vsrmc_checker_where_scan / _step_scan read stored levels only.  The levels beyond them (vsrmc_checker_deepen) exist as seen-set entries; their records
+ * pass through scratch buffers while a descent regenerates or inserts them, each state exactly once per descent, and the level after the inserted one —
+ * the probed level — has no records at all.  Programs ATTACHED to a checker are evaluated there, by every vsrmc_checker_deepen, and by every deepen
+ * inside vsrmc_checker_advance / vsrmc_check, while they are attached: with the attachment a user's state predicates see every state the built-in
+ * invariants see, and a user's step predicates every transition the search takes.  Nothing else changes: without an attachment every call, count and
+ * exit code is what it was, and with one the search itself (level infos, checksums, violations) is untouched.
+ * vsrmc_checker_deep_attach: state_prog (vsrmc_where_compile / vsrmc_predicates_compile) and / or step_prog (vsrmc_step_compile /
+ *   vsrmc_step_predicates_compile); either may be NULL, both NULL detaches.  The programs are copied: the caller may destroy its own.  VSRMC_E_ARG for a
+ *   step program in the state position and the reverse, and for a program compiled for another model; VSRMC_E_STATE on a sharded checker (world > 1) and
+ *   on an exact_ties checker.  While programs are attached vsrmc_checker_probe2 / _probe3 are refused (VSRMC_E_STATE).
+ *   Each seen-set-only level K is scanned EXACTLY ONCE, in the first descent after the attachment whose scratch buffers its records pass through: as a
+ *   regenerated level (kind 0) or as the inserted level (kind 1), slice by slice; the figures of the slices of a level accumulate.  The first deepen call
+ *   (the virtual level L+1) writes no records: its level is scanned when the next descent regenerates it, and a run that ends there has not examined it.
+ *   The same rule covers an attachment made after the deep search has begun and one made after vsrmc_checker_load: every level beyond the newest stored
+ *   one is scanned by the next descent.  The attachment is NOT part of a checkpoint (vsrmc_checker_save): attach again after loading.  A re-basing descent
+ *   scans what it regenerates, like any other.  vsrmc_checker_reset keeps the attachment and forgets its results.
+ *   State program: k_where over every slice.  Step program: k_step_list / k_step_apply over every slice = the transitions out of level K, those into the
+ *   probed level included.  The probed level (kind 2; state program only — the search takes no transition out of it): k_probe_where
+ *   (csrc/vsr_deep_where.hpp) evaluates the program on every successor of the inserted level's sub-slices that the seen-set does not hold, without writing
+ *   a record; when the pass is over the collected copies that are states of the inserted level after all are dropped and the rest de-duplicated by
+ *   fingerprint, the copy with the smallest key standing for the state (csrc/vsr_where_parse.hpp: departures).  A violation of a built-in invariant in
+ *   the inserted level ends the examination there: that pass reports no probed level.
+ * vsrmc_checker_deep_levels: the (level, probed) pairs that have results, ascending; levels == NULL asks for the number.  A level appears once as a
+ *   scanned level (probed = 0) and, one pass earlier, once as the probed level (probed = 1).
+ * vsrmc_checker_deep_result: the figures of one of them.  info->kind: 0 regenerated, 1 inserted, 2 probed.  w (may be NULL): vsrmc_where_info with
+ *   count / min_fp exact for kinds 0 and 1; n_states = the level's states (kind 2: the successors the program ran over, copies of one state counted each).
+ *   Kind 2: count[k] = DISTINCT states of the probed level that satisfy k; exact while the list of collected copies (2^20) did not overflow
+ *   (info->exact = 1), otherwise lower bounds (exact = 0) — never reported as exact; min_fp[k] is then the smallest among the copies that were kept, not necessarily
+ *   the level's smallest: a witness from it is a valid behaviour into a hit, but not the same one in every run.  s (may be NULL): vsrmc_step_info of the transitions out of the level
+ *   (kinds 0 and 1), n_pairs + n_err == `generated` of the level after it; count / min_fp exact.  min_index has no meaning for a transient level (~0);
+ *   min_ordinal / min_action are ~0 / -1: an ordinal is a position in the bag of the scratch record, which is gone (vsrmc_checker_deep_witness finds the
+ *   instance again).  kernel_ms / where_ms / step_ms are HOST times around the launches of a program, their synchronisation included.
+ * vsrmc_checker_deep_where_states / _deep_step_pairs: the hit lists of a level, in the order and under the contract of vsrmc_checker_where_states /
+ *   _step_pairs (the first 2^20 that arrive are kept, *n is the true number, VSRMC_E_REP beyond; the test knobs VSRMC_WHERE_LIST_CAP, VSRMC_STEP_LIST_CAP
+ *   and VSRMC_STEP_SLICE apply: the two caps are read at the attachment, the slice size at every slice; VSRMC_DEEP_INSTANCE_CAP=N, a test knob
+ *   with no other use, lowers the 2^22 entries of the attachment's instance list to N >= 64, so that a sub-slice overflows it and is run again in halves).  The ordinals of the pairs are positions in the scratch records of THIS descent.  Lists are kept
+ *   for the levels the last scanning descent scanned; an earlier level's list is dropped (VSRMC_E_STATE), its figures stay.  Kind 2 with exact = 0:
+ *   VSRMC_E_REP, *n = the copies offered.
+ * vsrmc_checker_deep_witness: a behaviour Init .. hit, the same one in every run; the layout of vsrmc_checker_trace.  which_program 0: the state with
+ *   the smallest fingerprint of the scanned level that satisfies state predicate k (vsrmc_checker_trace_fp — which accepts seen-set-only levels).
+ *   which_program 2: the same in the level as a PROBED level: the parent is the state of the level below whose fingerprint ends in the 45 bits the
+ *   state's smallest key keeps (an ambiguous pointer is reported as by vsrmc_checker_trace_to_violator), then the state itself.  which_program 1: the
+ *   behaviour into the parent with the smallest fingerprint that has a pair satisfying step predicate k, then the successor of the LOWEST-ORDINAL instance
+ *   of the replayed parent record whose pair has bit k (n_states = level + 1, actions[level] its action id). */
+typedef struct vsrmc_deep_info {
+  int32_t level, kind;                             /* kind: 0 regenerated, 1 inserted, 2 probed */
+  int32_t exact;                                   /* 1: every figure is exact; 0 (kind 2 only): the counts are lower bounds */
+  int32_t has_state, has_step, reserved0;          /* which programs were evaluated on this level */
+  uint64_t slices;                                 /* scratch slices of the level that were scanned */
+  uint64_t n_hit_states, n_hit_pairs;              /* states / pairs with any bit set: what the list calls report as *n */
+  double where_ms, step_ms;
+} vsrmc_deep_info;
+int32_t vsrmc_checker_deep_attach(vsrmc_checker* c, const vsrmc_where* state_prog, const vsrmc_where* step_prog);
+int32_t vsrmc_checker_deep_levels(vsrmc_checker* c, int32_t* levels, int32_t* probed, uint64_t cap, uint64_t* n);
+int32_t vsrmc_checker_deep_result(vsrmc_checker* c, int32_t level, int32_t probed, vsrmc_deep_info* info, vsrmc_where_info* w, vsrmc_step_info* s);
+int32_t vsrmc_checker_deep_where_states(vsrmc_checker* c, int32_t level, int32_t probed, uint64_t* fps, uint8_t* bits, uint64_t cap, uint64_t* n);
+int32_t vsrmc_checker_deep_step_pairs(vsrmc_checker* c, int32_t level, uint64_t* fps, uint32_t* ordinals, uint8_t* bits, uint64_t cap, uint64_t* n);
+int32_t vsrmc_checker_deep_witness(vsrmc_checker* c, int32_t level, int32_t which_program, int32_t k, uint64_t* words, uint64_t cap_words, uint64_t* off,
+                                   int32_t* actions, uint64_t cap_states, uint64_t* n_states);
+
 /* ≙ TLC's checkpoints (ModelChecker.checkpoint → FPSet.beginChkpt/commitChkpt, StateQueue and TLCTrace checkpoints; `-recover`):
  * one file holds the search between two levels — the occupied seen-set slots, the newest stored frontier, what the automatic level scheme
  * has learnt and, once the search has gone beyond the record buffers (vsrmc_checker_deepen), the descriptors of the levels that exist in

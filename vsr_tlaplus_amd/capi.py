@@ -62,6 +62,11 @@ class StepInfo(C.Structure):
                 ("min_action", C.c_int32 * 8), ("kernel_ms", C.c_double), ("list_ms", C.c_double), ("apply_ms", C.c_double), ("slices", C.c_uint64)]
 
 
+class DeepInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("kind", C.c_int32), ("exact", C.c_int32), ("has_state", C.c_int32), ("has_step", C.c_int32), ("reserved0", C.c_int32),
+                ("slices", C.c_uint64), ("n_hit_states", C.c_uint64), ("n_hit_pairs", C.c_uint64), ("where_ms", C.c_double), ("step_ms", C.c_double)]
+
+
 class ShardIO(C.Structure):
     _fields_ = [("cand_send", C.c_void_p), ("cand_cap", C.c_uint64)]
 
@@ -154,6 +159,12 @@ SYMBOLS = {
     "vsrmc_checker_step_scan": (C.c_int32, [V, V, C.POINTER(StepInfo)]),
     "vsrmc_checker_step_successor": (C.c_int32, [V, C.c_uint64, C.c_uint32, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "vsrmc_checker_step_pairs": (C.c_int32, [V, V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_attach": (C.c_int32, [V, V, V]),
+    "vsrmc_checker_deep_levels": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_result": (C.c_int32, [V, C.c_int32, C.c_int32, C.POINTER(DeepInfo), C.POINTER(WhereInfo), C.POINTER(StepInfo)]),
+    "vsrmc_checker_deep_where_states": (C.c_int32, [V, C.c_int32, C.c_int32, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_step_pairs": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_witness": (C.c_int32, [V, C.c_int32, C.c_int32, C.c_int32, V, C.c_uint64, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_check": (C.c_int32, [V, C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(LevelInfo)]),
     "vsrmc_queue_create": (C.c_int32, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(V)]),
     "vsrmc_queue_enqueue_batch": (C.c_int32, [V, V, V, C.c_uint64]),

@@ -434,6 +434,8 @@ class ModelChecker:
         """recover: path of a checkpoint written by save() — continue that search (≙ `tlc2.TLC -recover`).
         table_log2 = 0 / frontier_words = 0 / frontier_states = 0 / pending_entries = 0: sized from the free device memory (auto())."""
         self.model = model
+        self._deep = None                                            # (state Where, step Where) of deep_attach, or None
+        self._deep_seen = set()                                      # (level, probed) pairs run(deep=True) has looked at
         o = capi.Options()
         capi.load().vsrmc_options_default(C.byref(o))
         o.device, o.table_log2 = device, table_log2
@@ -575,7 +577,8 @@ class ModelChecker:
             check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))
         return st.value
 
-    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False, reach=None, never=None, step_never=None, step_reach=None):
+    def run(self, max_depth=None, max_seconds=None, stop_on_violation=True, check_deadlock=False, reach=None, never=None, step_never=None, step_reach=None,
+            deep=False):
         """Worker.run until the queue is empty, an invariant is violated, or a bound is hit — the automatic level scheme: levels are
         stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen).
         check_deadlock (TLC's default, off here): every stored level is scanned for terminal states before it is expanded; the first level
@@ -586,9 +589,25 @@ class ModelChecker:
         step_never / step_reach (a step Where each — Model.compile_step / compile_step_predicates — off by default): every stored level is step-scanned (step_scan: every
         transition out of it) before it is expanded, after the scans above.  A pair that satisfies a predicate of step_never ends the run with
         "violation", one that satisfies step_reach with "reached"; self.witness then names the PARENT (level, fp, index) and has `ordinal` and
-        `action` besides; step_witness_trace() is the behaviour with the step at its end."""
+        `action` besides; step_witness_trace() is the behaviour with the step at its end.
+        deep=True: the predicates are also ATTACHED (deep_attach) — one state program (`never` or `reach`, not both) and one step program (`step_never` or
+        `step_reach`) — so that the levels beyond the record buffers are examined as well; the run ends at the advance() that finds a hit.  The shallowest
+        level wins; within a level a built-in violation, then never, reach, step_never, step_reach.  self.witness then has `kind_of_level` in
+        ("regenerated", "inserted", "probed") and index None (a step hit: no ordinal either); deep_witness_trace() is the behaviour."""
         import time
         t0 = time.time()
+        deep_state = deep_step = None
+        if deep:
+            if never is not None and reach is not None:
+                raise ValueError("run(deep=True) attaches one state program: never or reach")
+            if step_never is not None and step_reach is not None:
+                raise ValueError("run(deep=True) attaches one step program: step_never or step_reach")
+            deep_state = (never, "violation", 1) if never is not None else (reach, "reached", 2) if reach is not None else None
+            deep_step = (step_never, "violation", 3) if step_never is not None else (step_reach, "reached", 4) if step_reach is not None else None
+            if deep_state is None and deep_step is None:
+                raise ValueError("run(deep=True) needs a predicate")
+            self.deep_attach(deep_state[0] if deep_state else None, deep_step[0] if deep_step else None)
+            self._deep_seen = set()
         while True:
             if max_depth is not None and self.depth >= max_depth:
                 return "max-depth"
@@ -621,10 +640,39 @@ class ModelChecker:
                                             ordinal=t["min_ordinal"][k], action=ACTION_NAMES[t["min_action"][k]])
                         return kind
             kind, d, p = self.advance()
+            if deep and kind == "deep":
+                hit = self._deep_first_hit(deep_state, deep_step, stop_on_violation)
+                if hit is not None:
+                    return hit
             if d["n_new"] == 0:
                 return "exhausted"
             if self.violation is not None and stop_on_violation:
                 return "violation"
+
+    def _deep_first_hit(self, deep_state, deep_step, stop_on_violation):
+        """the results of the levels the last advance() examined for the first time -> the run's verdict, or None"""
+        best = None
+        if self.violation is not None and stop_on_violation:
+            best = (self.violation["level"], 0, None, "violation")
+        for r in self.deep_results():
+            key = (r["level"], r["kind"] == "probed")
+            if key in self._deep_seen:
+                continue
+            self._deep_seen.add(key)
+            for prog, part in ((deep_state, r["state"]), (deep_step, r["step"])):
+                if prog is None or part is None:
+                    continue
+                w, verdict, order = prog
+                hits = [k for k in range(len(w.names)) if part["count"][k]]
+                if hits and (best is None or (r["level"], order) < best[:2]):
+                    k = hits[0]
+                    best = (r["level"], order, dict(level=r["level"], k=k, name=w.names[k], fp=part["min_fp"][k], index=None, kind=verdict,
+                                                    kind_of_level=r["kind"], program="step" if w.step else "state", exact=r["exact"]), verdict)
+        if best is None:
+            return None
+        if best[2] is not None:
+            self.witness = best[2]
+        return best[3]
 
     def violation_trace(self):
         """the counter-example of the violation run() / advance() reported, wherever it was found"""
@@ -828,6 +876,99 @@ class ModelChecker:
         n = C.c_uint64()
         check(capi.load().vsrmc_checker_trace(self._h, level, index, _p(words), cap_w, _p(off), _p(acts), len(off),
                                               C.byref(n)))
+        return [(ACTION_NAMES[acts[t]], words[int(off[t]): int(off[t + 1])].copy()) for t in range(n.value)]
+
+    DEEP_KINDS = ("regenerated", "inserted", "probed")
+
+    def deep_attach(self, state=None, step=None):
+        """Attach a state Where and / or a step Where to the search beyond the record buffers (vsrmc_checker_deep_attach): every deepen() — and every
+        deepen inside advance() / run() / check() — then evaluates them on the levels that exist in the seen-set only, each level once, and the state
+        program on the probed level as well (k_probe_where).  Both None detaches.  Results: deep_results()."""
+        check(capi.load().vsrmc_checker_deep_attach(self._h, state._h if state is not None else None, step._h if step is not None else None))
+        self._deep = (state, step) if (state is not None or step is not None) else None
+
+    def deep_results(self):
+        """The per-level results of the attached programs, ascending by (level, probed) -> [dict(level, kind in DEEP_KINDS, exact, slices, n_hit_states,
+        n_hit_pairs, where_ms, step_ms, state=dict(n_states, count[k], min_fp[k]) or None, step=dict(n_states, n_pairs, n_err, count[k], min_fp[k], slices)
+        or None)].  kind "probed": count[k] = distinct states, lower bounds when exact is False."""
+        lib = capi.load()
+        n = C.c_uint64()
+        check(lib.vsrmc_checker_deep_levels(self._h, None, None, 0, C.byref(n)))
+        lv = np.zeros(max(1, n.value), dtype=np.int32)
+        pr = np.zeros(max(1, n.value), dtype=np.int32)
+        check(lib.vsrmc_checker_deep_levels(self._h, _p(lv), _p(pr), len(lv), C.byref(n)))
+        if self._deep is None:
+            raise ValueError("no predicates are attached (deep_attach)")
+        state, step = self._deep
+        none = (1 << 64) - 1
+        out = []
+        for i in range(n.value):
+            d, w, s = capi.DeepInfo(), capi.WhereInfo(), capi.StepInfo()
+            check(lib.vsrmc_checker_deep_result(self._h, int(lv[i]), int(pr[i]), C.byref(d), C.byref(w), C.byref(s)))
+            r = dict(level=d.level, kind=self.DEEP_KINDS[d.kind], exact=bool(d.exact), slices=int(d.slices), n_hit_states=int(d.n_hit_states),
+                     n_hit_pairs=int(d.n_hit_pairs), where_ms=d.where_ms, step_ms=d.step_ms, state=None, step=None)
+            if d.has_state:
+                ns = len(state.names)
+                r["state"] = dict(n_states=int(w.n_states), count=[int(w.count[k]) for k in range(ns)],
+                                  min_fp=[None if w.min_fp[k] == none else int(w.min_fp[k]) for k in range(ns)])
+            if d.has_step:
+                ns = len(step.names)
+                r["step"] = dict(n_states=int(s.n_states), n_pairs=int(s.n_pairs), n_err=int(s.n_err), count=[int(s.count[k]) for k in range(ns)],
+                                 min_fp=[None if s.min_fp[k] == none else int(s.min_fp[k]) for k in range(ns)], slices=int(s.slices))
+            out.append(r)
+        return out
+
+    def deep_where_states(self, level, probed=False):
+        """The states of a level deep_results() lists that satisfy any state predicate -> (fingerprints ascending, their bits); the contract of
+        where_states() (VsrmcError -5 when the list overflowed)."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_deep_where_states(self._h, level, int(probed), None, None, 0, C.byref(n))
+        if rc not in (0, -5):
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        bits = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_deep_where_states(self._h, level, int(probed), _p(fps), _p(bits), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), bits[: n.value].copy()
+
+    def deep_step_pairs(self, level):
+        """The pairs out of a level deep_results() lists that satisfy any step predicate -> (parent fingerprints, ordinals, bits), by (fingerprint,
+        ordinal); the ordinals are positions in the scratch records of the descent that scanned the level."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_deep_step_pairs(self._h, level, None, None, None, 0, C.byref(n))
+        if rc not in (0, -5):
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        ords = np.zeros(max(1, n.value), dtype=np.uint32)
+        bits = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_deep_step_pairs(self._h, level, _p(fps), _p(ords), _p(bits), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), ords[: n.value].copy(), bits[: n.value].copy()
+
+    def deep_witness_trace(self, level=None, program=None, k=None, probed=False):
+        """The behaviour from Init into a hit of an attached program (vsrmc_checker_deep_witness), the same one in every run: [(action name, record)].
+        No arguments: the witness run(deep=True) stopped at.  Otherwise program "state" (probed=True: the level as a probed level) or "step" (the
+        behaviour into the parent plus the successor of the pair) and k, a number or a name."""
+        if level is None:
+            wit = self.witness
+            if wit is None or "kind_of_level" not in wit:
+                raise ValueError("run(deep=True) has not stopped at a hit beyond the record buffers")
+            level, program, k, probed = wit["level"], wit["program"], wit["k"], wit["kind_of_level"] == "probed"
+        if self._deep is None:
+            raise ValueError("no predicates are attached (deep_attach)")
+        w = self._deep[0 if program == "state" else 1]
+        if w is None:
+            raise ValueError("no %s program is attached" % program)
+        if not isinstance(k, int):
+            k = w.names.index(k)
+        which = 1 if program == "step" else 2 if probed else 0
+        lay = self.model.layout
+        cap_w = (level + 3) * int(lay.max_record_words)
+        words = np.zeros(cap_w, dtype=np.uint64)
+        off = np.zeros(level + 4, dtype=np.uint64)
+        acts = np.zeros(level + 4, dtype=np.int32)
+        n = C.c_uint64()
+        check(capi.load().vsrmc_checker_deep_witness(self._h, level, which, k, _p(words), cap_w, _p(off), _p(acts), len(off), C.byref(n)))
         return [(ACTION_NAMES[acts[t]], words[int(off[t]): int(off[t + 1])].copy()) for t in range(n.value)]
 
     def probe(self):

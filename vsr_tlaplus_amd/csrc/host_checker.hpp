@@ -14,6 +14,7 @@ struct PassDst {            // where a pass writes (records, refs, fingerprints)
   bool own_index = true;    //                                      false = `off` / `fp` are the idle frontier's own arrays
 };
 struct DeepLevelRec { u64 n_new = 0, n_local = 0, generated = 0, max_bag = 0, frontier = 0; };   // n_local: this rank's share (unsharded: all)   // a level that exists in the seen-set only (vsr_deep.hpp)
+struct vsrmc_deep_attach;    // a user's predicates on the levels beyond the record buffers (host_deep_where.hpp)
 struct vsrmc_checker {
   vsrmc_model model;
   vsrmc_options opt;
@@ -121,6 +122,7 @@ struct vsrmc_checker {
   std::vector<uint8_t> step_bits;
   u64 step_total = 0;
   int step_level = -1;
+  vsrmc_deep_attach* deep_attach = nullptr;   // vsrmc_checker_deep_attach (host_deep_where.hpp): programs, persistent device buffers, per-level results; not part of a checkpoint
 #ifdef VSRMC_TEST_HOOKS
   // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
   std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending
@@ -130,6 +132,15 @@ struct vsrmc_checker {
 };
 
 namespace {
+// host_deep_where.hpp (defined there: it needs the predicate kernels' host side): a search that starts over forgets what the attachment has scanned;
+// a checker that is destroyed frees it
+void deep_attach_restart(vsrmc_checker* c);
+void deep_attach_free(vsrmc_checker* c);
+// ... and the three places a descent of the deep search (vsr_deep.hpp) calls while programs are attached: before it starts, for every scratch slice of
+// a level (kind 0: regenerated, 1: inserted; probe_next: the successors of the slice are the probed level), and when it is over (rc: how it ended)
+int deep_where_begin(vsrmc_checker* c, int last_level);
+int deep_where_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, int kind, u64 bag, bool probe_next);
+int deep_where_end(vsrmc_checker* c, int rc);
 typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*, u64, u64*, u64, LevelCtl*, int, int, u64*, u64, u32, u64*,
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,
@@ -390,6 +401,7 @@ int checker_seed(vsrmc_checker* c) {
   c->probe_viol.clear();
   c->probe_viol_key.clear();
   c->probe_viol_level = 0;
+  deep_attach_restart(c);
   return 0;
 }
 }  // namespace

@@ -499,7 +499,7 @@ int32_t vsrmc_checker_trace_fp(vsrmc_checker* c, int32_t level, uint64_t fp, uin
                                int32_t* actions, uint64_t cap_states, uint64_t* n_states) {
   if (!c || !words || !off || !actions || !n_states) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "sharded checker: walk the predecessor pointers with vsrmc_checker_lookup on every rank");
-  if (level < 1 || level > c->level) return fail(VSRMC_E_ARG, "no such level");
+  if (level < 1 || level > c->level + c->deep) return fail(VSRMC_E_ARG, "no such level");   // (a seen-set-only level is walked like any other: the walk needs no records)
   HIPCHK(hipSetDevice(c->opt.device));
   std::vector<u64> fps;
   int rc = walk_trace(c, fp, level, &fps);                     // through the seen-set, back to Init, on the device
@@ -531,6 +531,7 @@ int32_t vsrmc_checker_trace(vsrmc_checker* c, int32_t level, uint64_t index, uin
 void vsrmc_checker_destroy(vsrmc_checker* c) {
   if (!c) return;
   (void)hipSetDevice(c->opt.device);
+  deep_attach_free(c);
   if (c->table) (void)hipFree(c->table);
   for (int b = 0; b < 2; b++) {
     if (c->words[b]) (void)(((c->host_frontier >> b) & 1) ? hipHostFree(c->words[b]) : hipFree(c->words[b]));

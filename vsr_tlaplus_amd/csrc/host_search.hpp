@@ -131,6 +131,28 @@ int32_t vsrmc_checker_probe_trace(vsrmc_checker* c, uint64_t* words, uint64_t ca
   return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
 }
 
+}  // extern "C"
+namespace {
+// Init .. the state of level plevel - 1 whose fingerprint ends in the 45 bits `key` keeps of its parent, then the probed state `fp` itself: how every
+// state of a probed level is reached (vsrmc_checker_trace_to_violator, vsrmc_checker_deep_witness)
+int trace_by_parent_key(vsrmc_checker* c, u64 fp, u64 key, int plevel, uint64_t* words, uint64_t cap_words, uint64_t* off, int32_t* actions, uint64_t cap_states,
+                        uint64_t* n_states) {
+  HIPCHK(hipSetDevice(c->opt.device));
+  int found = 0;
+  u64 pfp = 0, pmeta = 0;
+  int rc = table_lookup(c, meta_pfp(key), plevel - 1, 1, &found, &pfp, &pmeta);
+  if (rc) return rc;
+  if (found > 1) return fail(VSRMC_E_STATE, "ambiguous predecessor pointer: several states of the parent's level share the 45 fingerprint bits the violating successor keeps of its parent");
+  if (!found) return fail(VSRMC_E_STATE, "the parent of this violating state is not in the seen-set");
+  std::vector<u64> fps;
+  rc = walk_trace(c, pfp, plevel - 1, &fps);
+  if (rc) return rc;
+  fps.push_back(fp);
+  return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
+}
+}  // namespace
+extern "C" {
+
 // TLCTrace.getTrace for a violating state of the caller's choice: the probe collects EVERY violating successor (vsrmc_checker_probe_violators) and reports the
 // one with the smallest fingerprint; the reference's own counter-example (state_transfer_violation_trace.txt:555-577) ends in another one of them.  The path:
 // Init .. the violator's parent — the state of the level below whose fingerprint ends in the 45 bits the smallest key among the violator's copies carries,
@@ -141,19 +163,7 @@ int32_t vsrmc_checker_trace_to_violator(vsrmc_checker* c, uint64_t fp, uint64_t*
   const auto it = std::lower_bound(c->probe_viol.begin(), c->probe_viol.end(), (u64)fp);
   if (it == c->probe_viol.end() || *it != fp || c->probe_viol_key.size() != c->probe_viol.size() || c->probe_viol_level < 2)
     return fail(VSRMC_E_STATE, "not a violating state of the last probed level (vsrmc_checker_probe_violators lists them)");
-  const u64 key = c->probe_viol_key[(size_t)(it - c->probe_viol.begin())];
-  HIPCHK(hipSetDevice(c->opt.device));
-  int found = 0;
-  u64 pfp = 0, pmeta = 0;
-  int rc = table_lookup(c, meta_pfp(key), c->probe_viol_level - 1, 1, &found, &pfp, &pmeta);
-  if (rc) return rc;
-  if (found > 1) return fail(VSRMC_E_STATE, "ambiguous predecessor pointer: several states of the parent's level share the 45 fingerprint bits the violating successor keeps of its parent");
-  if (!found) return fail(VSRMC_E_STATE, "the parent of this violating state is not in the seen-set");
-  std::vector<u64> fps;
-  rc = walk_trace(c, pfp, c->probe_viol_level - 1, &fps);
-  if (rc) return rc;
-  fps.push_back((u64)fp);
-  return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
+  return trace_by_parent_key(c, (u64)fp, c->probe_viol_key[(size_t)(it - c->probe_viol.begin())], c->probe_viol_level, words, cap_words, off, actions, cap_states, n_states);
 }
 
 int32_t vsrmc_checker_step(vsrmc_checker* c, vsrmc_level_info* info) {

@@ -310,6 +310,7 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
     sl.observe(n, part, c->h.words_new);
     if (regen) {
       R.ins.materialize_ms += c->expand_ms;                    // time spent regenerating (reported beside the level's own expansion)
+      if (c->deep_attach && !R.io && (rc = deep_where_slice(c, B, part, lv + 1, 0, out_bag, false)) != 0) return rc;   // attached predicates: a level is scanned in the first descent that regenerates it
       if (lv + 1 == R.last_regen && !R.insert) rc = R.rebase ? deep_export(R, B, part) : deep_probe(R, B, part, lv + 1, out_bag);
       else rc = deep_descend(R, B.words, B.off, part, out_bag, lv + 1, k + 1);
       if (rc) return rc;
@@ -340,6 +341,8 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
       R.ins.fp_sum += hsum[1];
       R.ins.n_new += hsum[2];                                  // the states that stayed (a sharded pass has withdrawn the announced ones that lost)
     }
+    // attached predicates: the sub-slice of the inserted level, its transitions, and (while the level is clean) its successors = the probed level
+    if (c->deep_attach && !R.io && (rc = deep_where_slice(c, B, part, lv + 1, 1, bag_new, R.viol_ins == ~(u64)0)) != 0) return rc;
     if (R.viol_ins != ~(u64)0) continue;                       // a violation in the inserted level: it is completed, nothing deeper is probed
     rc = deep_probe(R, B, part, lv + 1, bag_new);
     if (rc) return rc;
@@ -487,7 +490,10 @@ int deep_pass(vsrmc_checker* c, int last_regen, bool insert, vsrmc_level_info* i
   }
   if (rc) { c->failed = 1; return rc; }
   if (io) { u64 sync = 0; rc = io->any(io->ctx, &sync); }      // every rank has cleared its taken bits
+  const bool scan = c->deep_attach && !io;
+  if (!rc && scan) rc = deep_where_begin(c, last_regen + (insert ? 1 : 0));
   if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 0);
+  if (scan) rc = deep_where_end(c, rc);                        // (the inserted level is complete: the probed level's collected copies are resolved against it)
   if (rc) { c->failed = 1; return rc; }
   const u64 n_local = R.ins.n_new;
   R.ins.viol_fp = R.viol_ins;
@@ -585,7 +591,9 @@ int deep_rebase(vsrmc_checker* c, vsrmc_level_info* out) {
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   c->deep_regen_done = true;
-  rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 1);
+  rc = c->deep_attach ? deep_where_begin(c, K) : 0;             // a re-basing descent scans what it regenerates, like any other
+  if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 1);
+  if (c->deep_attach) rc = deep_where_end(c, rc);
   if (rc) { c->failed = 1; return rc; }
   u64 cnt[2] = {0, 0};
   u32 xerr = 0;
@@ -663,6 +671,7 @@ int32_t vsrmc_checker_deepen(vsrmc_checker* c, vsrmc_level_info* inserted, vsrmc
 int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_level_info* probe) {
   if (!c || !virt || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2 starts from a materialised level");
+  if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   vsrmc_level_info none;
   int rc = vsrmc_checker_deepen(c, virt, probe);
   if (rc || virt->viol_mask || virt->n_new == 0) return rc;
@@ -674,6 +683,7 @@ int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_lev
 int32_t vsrmc_checker_probe3(vsrmc_checker* c, vsrmc_level_info* virt1, vsrmc_level_info* virt2, vsrmc_level_info* probe) {
   if (!c || !virt1 || !virt2 || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3 starts from a materialised level");
+  if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   std::memset(virt2, 0, sizeof(*virt2));
   virt2->viol_fp = virt2->viol_index = ~(u64)0;
   int rc = vsrmc_checker_deepen(c, virt1, probe);

@@ -31,6 +31,10 @@
 //   * aux_svc and aux_client_acked are outside VIEW: of the states that differ only there the search keeps one representative (the smallest canonical
 //     auxkey), and a predicate on them sees that representative.  NOT SO ON A RANDOM WALK (vsr_sim_where.hpp): a walk has
 //     no VIEW representative; the aux variables a state program reads there are the walk's own — which is what TLC sees.
+//   * A state of the PROBED level of the search beyond the record buffers (vsr_deep_where.hpp) has no record: it is evaluated on the
+//     generated copy with the smallest key among the copies that satisfied a predicate.  Where the copies of one fingerprint differ in the aux variables
+//     (an F2 tie, which the pass that inserts the level reports), that copy is one that satisfied something — not necessarily the representative the
+//     level keeps when it is inserted; the scan of the inserted level one pass later sees the representative.
 //
 //   * (step predicates, below) the primed aux variables — aux_svc', aux_client_acked'[v] — are those of the successor AS THE ACTION GENERATES IT, before the
 //     search picks the representative of its VIEW class: a pair is (stored state, generated successor), not (stored state, stored state).

@@ -26,6 +26,7 @@
 #include "vsr_where.hpp"
 #include "vsr_where_parse.hpp"
 #include "vsr_step.hpp"
+#include "vsr_deep_where.hpp"
 #include "vsr_sim_where.hpp"
 
 #define VSRMC_FP_VERSION 2          // fingerprint function of this build; checkpoints of another version are refused
@@ -121,5 +122,6 @@ extern "C" {
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
+#include "host_deep_where.hpp"   // state / step predicates on the levels beyond the record buffers: attachment, per-level results, witnesses; k_probe_where
 #include "host_sim_where.hpp"    // simulation with state / step predicates on every walk: k_simulate_where
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

@@ -8,6 +8,7 @@
 // stored level without stopping.  -predicates FILE with -reach / -invariant / -whereReport evaluates the user's own state predicates (k_where) on every
 // stored level, where -checkDeadlock scans.  -steps FILE with -stepReach / -stepInvariant / -stepReport does the same for step predicates (primed variables:
 // csrc/vsr_step.hpp) over every transition out of every stored level.  With -simulate the same flags ask the same questions of random walks (csrc/vsr_sim_where.hpp).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +52,10 @@ static void usage() {
       "  -stepReach NAME[,NAME]      the same scan for NAME itself: exit 0 when a transition satisfies it, 14 when the search ended without one\n"
       "  -stepReport       per level the pairs, the instances that raise an evaluation error and the pairs that satisfy each exported name, without\n"
       "                    stopping; with -json a \"steps\" object in the level lines.  Levels that are never stored are not examined, and the report says how many\n"
+      "  -deepPredicates   with the flags above: the predicates are also evaluated on the levels beyond the record buffers (the Virtual / Probe lines) —\n"
+      "                    every regenerated and inserted level and the transitions out of them, and the state predicates on the probed level too.  Report\n"
+      "                    rows follow those lines; -reach / -invariant / -stepReach / -stepInvariant stop there with the messages and exit codes above.\n"
+      "                    Per kind of program either the report or the query flags; not with -gpus N > 1, -simulate, -probe2At / -probe3At\n"
       "  -maxDepth N       stop after N BFS levels (Init = level 1)\n"
       "  -device D         HIP device ordinal (default 0)\n"
       "  -gpus N           N > 1: run the sharded checker on N GPUs of this node (re-executes as\n"
@@ -142,8 +147,14 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
+  bool deep_predicates = false;
+  for (int i = 1; i < argc; i++)
+    if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
   for (int i = 1; i + 1 < argc; i++)
-    if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) return exec_sharded(argc, argv, i);
+    if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) {
+      if (deep_predicates) { std::fprintf(stderr, "Error: -deepPredicates runs on one GPU: sharded checkers are not scanned (-gpus 1)\n"); return 2; }
+      return exec_sharded(argc, argv, i);
+    }
   std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, steps_file, step_reach_arg, step_invariant_arg;
   bool where_report = false, step_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
@@ -199,11 +210,25 @@ int main(int argc, char** argv) {
     else if (a == "-stepReach" && i + 1 < argc) step_reach_arg = argv[++i];
     else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
     else if (a == "-stepReport") step_report = true;
+    else if (a == "-deepPredicates") deep_predicates = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
   }
   if (cfg.empty()) { usage(); return 2; }
+  if (deep_predicates) {                                          // refused before any device call
+    const bool state_query = !reach_arg.empty() || !invariant_arg.empty(), step_query = !step_reach_arg.empty() || !step_invariant_arg.empty();
+    if (!state_query && !where_report && !step_query && !step_report) {
+      std::fprintf(stderr, "Error: -deepPredicates needs -reach / -invariant / -whereReport (with -predicates FILE) or -stepReach / -stepInvariant / -stepReport (with -steps FILE)\n");
+      return 2;
+    }
+    if (simulate) { std::fprintf(stderr, "Error: -deepPredicates belongs to the exhaustive search: -simulate evaluates the predicates on its walks\n"); return 2; }
+    if (probe2_at > 0 || probe3_at > 0) { std::fprintf(stderr, "Error: -deepPredicates cannot be combined with -probe2At / -probe3At\n"); return 2; }
+    if ((state_query && where_report) || (step_query && step_report)) {
+      std::fprintf(stderr, "Error: -deepPredicates attaches one program of each kind: either -whereReport or -reach / -invariant, either -stepReport or -stepReach / -stepInvariant\n");
+      return 2;
+    }
+  }
   vsrmc_model* m = nullptr;
   if (vsrmc_model_load(no_tla || tla.empty() ? nullptr : tla.c_str(), cfg.c_str(), &m) != 0) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
@@ -498,6 +523,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  vsrmc_where* const deep_state = !deep_predicates ? nullptr : w_query ? w_query : where_report ? w_all : nullptr;
+  vsrmc_where* const deep_step = !deep_predicates ? nullptr : s_query ? s_query : step_report ? s_all : nullptr;
+  if (deep_predicates && vsrmc_checker_deep_attach(c, deep_state, deep_step) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   static const char* const MODULES[3] = {"VSR.tla", "VR_STATE_TRANSFER.tla", "VR_APP_STATE.tla"};
   std::printf("vsrmc: %s lowered: ReplicaCount=%d ClientCount=%d |Values|=%d StartViewOnTimerLimit=%d, %d permutation(s), "
               "invariant mask %d\n", MODULES[lay.module >= 0 && lay.module < 3 ? lay.module : 0], lay.replica_count, lay.client_count, lay.value_count, lay.start_view_on_timer_limit,
@@ -583,6 +614,10 @@ int main(int argc, char** argv) {
     if (ti.n_unsettled && !uns_level) { uns_level = ti.level; uns_fp = ti.min_fp_unsettled; }
     return 0;
   };
+  // -deepPredicates: the (level, as the probed level) pairs the attached programs have examined.  A level that a descent scanned and that the search then
+  // re-based onto is a stored level from there on: it is not scanned, and not reported, a second time
+  std::vector<std::pair<int, int>> deep_seen;
+  auto deep_scanned = [&](int level) { return std::find(deep_seen.begin(), deep_seen.end(), std::make_pair(level, 0)) != deep_seen.end(); };
   // state predicates: the newest stored level is scanned where the terminal scan scans it
   struct WhereRow { int level; unsigned long long n_states; unsigned long long count[8]; };
   std::vector<WhereRow> where_rows;
@@ -597,6 +632,7 @@ int main(int argc, char** argv) {
     vsrmc_level_info st;
     if (vsrmc_checker_status(c, &st) != 0) return -1;
     if (st.reserved0 != 0 || st.level == where_last || st.n_new == 0) return 0;
+    if (deep_predicates && (w_query || where_report) && deep_scanned(st.level)) { where_last = st.level; return 0; }
     int32_t r = 0;
     if (w_all && where_report && (r = vsrmc_checker_where_scan(c, w_all, &wi_all)) != 0) return r == VSRMC_E_STATE ? 0 : r;
     if (w_query && (r = vsrmc_checker_where_scan(c, w_query, &wi_query)) != 0) return r == VSRMC_E_STATE ? 0 : r;
@@ -629,6 +665,7 @@ int main(int argc, char** argv) {
     vsrmc_level_info st;
     if (vsrmc_checker_status(c, &st) != 0) return -1;
     if (st.reserved0 != 0 || st.level == step_last || st.n_new == 0) return 0;
+    if (deep_predicates && (s_query || step_report) && deep_scanned(st.level)) { step_last = st.level; return 0; }
     int32_t r = 0;
     if (s_all && step_report && (r = vsrmc_checker_step_scan(c, s_all, &si_all)) != 0) return r == VSRMC_E_STATE ? 0 : r;
     if (s_query && (r = vsrmc_checker_step_scan(c, s_query, &si_query)) != 0) return r == VSRMC_E_STATE ? 0 : r;   // (last: vsrmc_checker_step_successor follows it)
@@ -693,6 +730,68 @@ int main(int argc, char** argv) {
         std::printf("Warning: cannot write %s\n", dump_trace_file.c_str());
     }
     return true;
+  };
+  // -deepPredicates: the levels the last pass examined for the first time (vsrmc_checker_deep_levels): report rows, and the first hit of a query
+  struct DeepHit { int level = 0, probed = 0, step = 0, k = -1, exact = 1; uint64_t fp = 0, count = 0, of = 0; } deep_hit;
+  std::vector<int> virtual_levels;
+  std::vector<int> deep_inexact;                                  // probed levels whose list of collected copies overflowed: their figures are lower bounds
+  std::vector<WhereRow> where_probed_rows;
+  std::vector<int> where_probed_exact;
+  static const char* const DEEP_KIND[3] = {"regenerated", "inserted", "probed"};
+  auto deep_collect = [&]() -> int {
+    uint64_t n = 0;
+    if (vsrmc_checker_deep_levels(c, nullptr, nullptr, 0, &n) != 0) return -1;
+    std::vector<int32_t> lv((size_t)n + 1), pr((size_t)n + 1);
+    if (vsrmc_checker_deep_levels(c, lv.data(), pr.data(), n, &n) != 0) return -1;
+    for (uint64_t i = 0; i < n && deep_hit.k < 0; i++) {
+      const std::pair<int, int> key(lv[i], pr[i]);
+      if (std::find(deep_seen.begin(), deep_seen.end(), key) != deep_seen.end()) continue;
+      deep_seen.push_back(key);
+      vsrmc_deep_info di;
+      vsrmc_where_info wi;
+      vsrmc_step_info si;
+      if (vsrmc_checker_deep_result(c, lv[i], pr[i], &di, &wi, &si) != 0) return -1;
+      if (!di.exact) deep_inexact.push_back(di.level);
+      std::string line;
+      if (di.has_state && where_report) {
+        WhereRow row{di.level, (unsigned long long)wi.n_states, {0}};
+        for (size_t k = 0; k < where_names.size(); k++) row.count[k] = (unsigned long long)wi.count[k];
+        if (di.kind == 2) { where_probed_rows.push_back(row); where_probed_exact.push_back(di.exact); }
+        else where_rows.push_back(row);
+        line += json ? ", \"where\": {" : "";
+        for (size_t k = 0; k < where_names.size(); k++)
+          line += json ? (k ? ", \"" : "\"") + where_names[k] + "\": " + std::to_string(row.count[k]) : ", " + where_names[k] + " " + std::to_string(row.count[k]);
+        line += json ? "}" : "";
+      }
+      if (di.has_step && step_report) {
+        StepRow row{di.level, (unsigned long long)si.n_states, (unsigned long long)si.n_pairs, (unsigned long long)si.n_err, {0}};
+        for (size_t k = 0; k < step_names.size(); k++) row.count[k] = (unsigned long long)si.count[k];
+        step_rows.push_back(row);
+        line += json ? ", \"steps\": {\"pairs\": " + std::to_string(row.n_pairs) + ", \"errors\": " + std::to_string(row.n_err) + ", \"count\": {"
+                     : "; " + std::to_string(row.n_pairs) + " pairs, " + std::to_string(row.n_err) + " errors";
+        for (size_t k = 0; k < step_names.size(); k++)
+          line += json ? (k ? ", \"" : "\"") + step_names[k] + "\": " + std::to_string(row.count[k]) : ", " + step_names[k] + " " + std::to_string(row.count[k]);
+        line += json ? "}}" : "";
+      }
+      if (!line.empty()) {
+        if (json) std::printf("{\"level\": %d, \"stored\": false, \"kind\": \"%s\", \"exact\": %s%s}\n", di.level, DEEP_KIND[di.kind], di.exact ? "true" : "false", line.c_str());
+        else std::printf("Examined(%d, %s%s)%s\n", di.level, DEEP_KIND[di.kind], di.exact ? "" : ", lower bounds", line.c_str());
+      }
+      // a query: an invariant's violation before a reachability hit, state predicates before step predicates, as on a stored level
+      if (di.has_state && w_query) {
+        int hit = -1;
+        for (size_t k = n_reach; k < query_names.size() && hit < 0; k++) if (wi.count[k]) hit = (int)k;
+        for (size_t k = 0; k < n_reach && hit < 0; k++) if (wi.count[k]) hit = (int)k;
+        if (hit >= 0) { deep_hit.level = di.level; deep_hit.probed = di.kind == 2; deep_hit.step = 0; deep_hit.k = hit; deep_hit.exact = di.exact; deep_hit.fp = wi.min_fp[hit]; deep_hit.count = wi.count[hit]; deep_hit.of = wi.n_states; }
+      }
+      if (deep_hit.k < 0 && di.has_step && s_query) {
+        int hit = -1;
+        for (size_t k = n_step_reach; k < step_query_names.size() && hit < 0; k++) if (si.count[k]) hit = (int)k;
+        for (size_t k = 0; k < n_step_reach && hit < 0; k++) if (si.count[k]) hit = (int)k;
+        if (hit >= 0) { deep_hit.level = di.level; deep_hit.probed = 0; deep_hit.step = 1; deep_hit.k = hit; deep_hit.fp = si.min_fp[hit]; deep_hit.count = si.count[hit]; deep_hit.of = si.n_pairs; }
+      }
+    }
+    return 0;
   };
   while (depth < max_depth) {
     if ((probe2_at > 0 && depth + 1 == probe2_at) || (probe3_at > 0 && depth + 1 == probe3_at)) {
@@ -763,8 +862,9 @@ int main(int argc, char** argv) {
       depth = info.level;
       rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
       if (terminal_report && !scanned_this_step) { unlisted_levels++; unlisted_deadlocks += (unsigned long long)info.deadlocks; }   // the level this pass expanded has no records
-      if (w_all) where_unexamined++;                              // the level this pass inserted is never stored
-      if (s_all) step_unexamined++;
+      if (w_all && !deep_state) where_unexamined++;               // the level this pass inserted is never stored
+      if (s_all && !deep_step) step_unexamined++;
+      virtual_levels.push_back(info.level);
       if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -787,6 +887,10 @@ int main(int argc, char** argv) {
           viol_level = (uint64_t)probed.level;
           break;
         }
+      }
+      if (deep_predicates) {
+        if (deep_collect() != 0) { rc = -1; break; }
+        if (deep_hit.k >= 0) break;
       }
       checkpoint_now(info.level);
       continue;
@@ -828,12 +932,21 @@ int main(int argc, char** argv) {
   // the report covers the newest stored level too when the loop ended before expanding it (-maxDepth, a violation, a full seen-set); an exhausted search's
   // last level is empty and a level already scanned is not scanned again (scan_newest)
   if (terminal_report && rc == 0 && !deadlocked) rc = scan_newest();
-  if (s_all && rc == 0 && step_hit < 0 && where_hit < 0 && !deadlocked && !violated && !probed_violation) {
+  if (deep_predicates && rc == 0) {                               // which never-stored levels stayed unexamined (by number): those of a run that ends after the virtual level
+    for (int lvl : virtual_levels) {
+      const bool scanned = std::find(deep_seen.begin(), deep_seen.end(), std::make_pair(lvl, 0)) != deep_seen.end();
+      const bool probed = std::find(deep_seen.begin(), deep_seen.end(), std::make_pair(lvl, 1)) != deep_seen.end();
+      if (deep_state && !scanned && !probed) where_unexamined++;
+      if (deep_step && !scanned) step_unexamined++;
+      if ((deep_state && !scanned && !probed) || (deep_step && !scanned)) std::printf("Level %d was never stored and no later pass regenerated it: not examined.\n", lvl);
+    }
+  }
+  if (s_all && rc == 0 && step_hit < 0 && where_hit < 0 && deep_hit.k < 0 && !deadlocked && !violated && !probed_violation) {
     rc = step_newest();
     if (json && step_report && step_scanned_this_step && rc == 0)       // the newest level was not expanded: a line of its own
       std::printf("{\"level\": %d, \"expanded\": false, %s}\n", si_all.level, step_json_of().c_str());
   }
-  if (w_all && rc == 0 && where_hit < 0 && !deadlocked) {
+  if (w_all && rc == 0 && where_hit < 0 && deep_hit.k < 0 && !deadlocked) {
     rc = where_newest();
     if (json && where_report && where_scanned_this_step && rc == 0) {   // the newest level was not expanded: a line of its own
       std::printf("{\"level\": %d, \"expanded\": false, \"where\": {", wi_all.level);
@@ -874,6 +987,48 @@ int main(int argc, char** argv) {
           std::printf("Warning: cannot write %s\n", dump_trace_file.c_str());
       }
       exit_code = 12;   // TLC's exit code for a safety violation
+    }
+  } else if (deep_hit.k >= 0) {                                 // -deepPredicates: a hit beyond the record buffers, with the messages and exit codes of the stored path
+    const bool inv = deep_hit.step ? deep_hit.k >= (int)n_step_reach : deep_hit.k >= (int)n_reach;
+    const char* name = deep_hit.step ? step_query_names[deep_hit.k].c_str() : query_names[deep_hit.k].c_str();
+    if (inv) std::printf(deep_hit.step ? "Error: Action property %s is violated.\n" : "Error: Invariant %s is violated.\n", name);
+    else if (deep_hit.step)
+      std::printf("Step satisfying %s found at depth %d (%llu of the level's %llu transitions satisfy it).\n", name, deep_hit.level, (unsigned long long)deep_hit.count,
+                  (unsigned long long)deep_hit.of);
+    else if (deep_hit.probed)
+      std::printf("State satisfying %s found at depth %d (%s%llu states of the probed level satisfy it).\n", name, deep_hit.level, deep_hit.exact ? "" : "at least ",
+                  (unsigned long long)deep_hit.count);
+    else
+      std::printf("State satisfying %s found at depth %d (%llu of the level's %llu states satisfy it).\n", name, deep_hit.level, (unsigned long long)deep_hit.count,
+                  (unsigned long long)deep_hit.of);
+    const uint64_t cap_w = ((uint64_t)deep_hit.level + 3) * (uint64_t)lay.max_record_words;
+    uint64_t n_states = 0;
+    std::vector<uint64_t> words(cap_w), off((size_t)deep_hit.level + 4);
+    std::vector<int32_t> acts((size_t)deep_hit.level + 4);
+    if (vsrmc_checker_deep_witness(c, deep_hit.level, deep_hit.step ? 1 : deep_hit.probed ? 2 : 0, deep_hit.k, words.data(), cap_w, off.data(), acts.data(), off.size() - 1,
+                                   &n_states) != 0) {
+      std::printf("Error: %s\n", vsrmc_last_error());
+      exit_code = 1;
+    } else {
+      if (json && deep_hit.step)
+        std::printf("{\"%s\": \"%s\", \"level\": %d, \"parent_fp\": \"%016llx\", \"action\": \"%s\", \"pairs\": %llu}\n", inv ? "action_property_violated" : "step_reached", name,
+                    deep_hit.level, (unsigned long long)deep_hit.fp, vsrmc_action_name(acts[n_states - 1]), (unsigned long long)deep_hit.count);
+      std::printf("%s\n", inv ? "Error: The behavior up to this point is:" : "The behavior up to this point is:");
+      for (uint64_t t = 0; t < n_states; t++) {
+        int64_t need = 0;
+        vsrmc_model_format_state(m, &words[off[t]], nullptr, 0, &need);
+        std::string buf((size_t)need, '\0');
+        vsrmc_model_format_state(m, &words[off[t]], &buf[0], need, &need);
+        std::printf("State %llu: <%s>\n%s\n\n", (unsigned long long)(t + 1), vsrmc_action_name(acts[t]), buf.c_str());
+      }
+      if (deep_hit.step) std::printf("The last step is %s of State %d.\n", vsrmc_action_name(acts[n_states - 1]), deep_hit.level);
+      if (!dump_trace_file.empty()) {
+        if (write_trace_expression(dump_trace_file, m, words, off, acts, n_states))
+          std::printf("The counter-example was written to %s (TLA+ trace expression).\n", dump_trace_file.c_str());
+        else
+          std::printf("Warning: cannot write %s\n", dump_trace_file.c_str());
+      }
+      exit_code = inv ? 12 : 0;
     }
   } else if (where_hit >= (int)n_reach) {                       // a user's invariant: reported like a built-in one
     std::printf("Error: Invariant %s is violated.\n", query_names[where_hit].c_str());
@@ -936,14 +1091,14 @@ int main(int argc, char** argv) {
                   "terminal state could still violate it; loops are not examined).\n");
     }
   }
-  if (n_reach && rc == 0 && where_hit < 0 && !violated && !probed_violation && !deadlocked) {
+  if (n_reach && rc == 0 && where_hit < 0 && deep_hit.k < 0 && !violated && !probed_violation && !deadlocked) {
     for (size_t k = 0; k < n_reach; k++)
       std::printf("No state satisfying %s was found in the %s.\n", query_names[k].c_str(),
                   where_unexamined ? "levels that were examined" : info.n_new == 0 && !incomplete ? "state space" : "levels searched");
     if (where_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.\n", where_unexamined);
     exit_code = exit_code ? exit_code : 14;
   }
-  if (n_step_reach && rc == 0 && step_hit < 0 && where_hit < 0 && !violated && !probed_violation && !deadlocked) {
+  if (n_step_reach && rc == 0 && step_hit < 0 && where_hit < 0 && deep_hit.k < 0 && !violated && !probed_violation && !deadlocked) {
     for (size_t k = 0; k < n_step_reach; k++)
       std::printf("No step satisfying %s was found in the %s.\n", step_query_names[k].c_str(),
                   step_unexamined ? "levels that were examined" : info.n_new == 0 && !incomplete ? "state space" : "levels searched");
@@ -985,8 +1140,31 @@ int main(int argc, char** argv) {
         if (r.count[k]) { std::printf("%slevel %d: %llu", first ? " (" : ", ", r.level, r.count[k]); first = false; }
       std::printf("%s.\n", first ? "" : ")");
     }
+    for (size_t i = 0; i < where_probed_rows.size(); i++) {       // a probed level that no later pass inserted: its figures stand alone (distinct states)
+      const WhereRow& r = where_probed_rows[i];
+      bool later = false;
+      for (const WhereRow& q : where_rows) later = later || q.level == r.level;
+      if (later) continue;
+      std::printf("Where report: probed level %d (%s)", r.level, where_probed_exact[i] ? "exact" : "lower bounds: the list of collected copies overflowed");
+      for (size_t k = 0; k < where_names.size(); k++) std::printf(", %s %llu", where_names[k].c_str(), r.count[k]);
+      std::printf(".\n");
+    }
     if (where_unexamined) std::printf("%llu level(s) were never stored (the Virtual lines): not examined.  Probed levels are not examined either.\n", where_unexamined);
     if (probe2_at > 0 || probe3_at > 0) std::printf("The levels of -probe2At / -probe3At were not examined: they have no records.\n");
+  }
+  if (deep_predicates && rc == 0 && !deep_seen.empty()) {
+    int through_states = 0, through_steps = 0;
+    for (const auto& kv : deep_seen) { through_states = std::max(through_states, kv.first); if (!kv.second) through_steps = std::max(through_steps, kv.first); }
+    if (deep_state && deep_step) std::printf("Beyond the record buffers, states were examined through level %d and the transitions out of the levels through %d.\n", through_states, through_steps);
+    else if (deep_state) std::printf("Beyond the record buffers, states were examined through level %d.\n", through_states);
+    else std::printf("Beyond the record buffers, the transitions out of the levels through %d were examined.\n", through_steps);
+    for (int lvl : deep_inexact) {
+      bool later = false;                                         // (a later pass that inserted the level scanned every state of it)
+      for (const auto& kv : deep_seen) later = later || (kv.first == lvl && kv.second == 0);
+      if (!later)
+        std::printf("Probed level %d: the list of collected copies overflowed — its counts are lower bounds, and a predicate that holds in few of its states may "
+                    "have been missed there.\n", lvl);
+    }
   }
   if (coverage) {   // ≙ tlc2.TLC -coverage, per action of Next: successors generated in the stored levels (probed / virtual levels not included)
     std::printf("The coverage statistics (successors generated per action):\n");
