@@ -193,33 +193,156 @@ EXPECTED = {
     (5, 1, 1, 2): (A_SendSV, A_ReceiveSV, A_ReceiveHigherDVC),
     (4, 1, 1, 2): (A_SendSV, A_ReceiveSV, A_ReceiveHigherDVC),
 }
+
+# the TWO-CLIENT spaces (tests/test_two_clients_cpu.py, test_two_clients_gpu.py): three replicas, run under the documented policy assume_commit_number (the
+# strict reading of VSR.tla:421 aborts on the first ReceivePrepareMsg at ClientCount = 2).  (3,2,3,1) and (3,2,3,2) are SPEC 323 - BASELINE configs[3]'s
+# instantiation of k_expand - and (3,2,2,1) a generic one.  Five levels of normal operation before the view change put entries of both clients into the logs
+# the view change merges.
+A_ReceivePrepareMsg = 10
+COUNTED_C2 = COUNTED + (A_ReceivePrepareMsg,)
+SPACES_C2 = {
+    (3, 2, 3, 1): (("st", dict(prefix_levels=5)), ("vc", {})),
+    (3, 2, 3, 2): (("st", dict(prefix_levels=5)), ("vc", {})),
+    (3, 2, 2, 1): (("st", dict(prefix_levels=5)), ("vc", {})),
+}
+FLOOR_C2 = 500                                                      # directly compared instances per action of COUNTED_C2, over the three spaces together
+FLOOR_C2_FLIPS = 800                                                # (3,2,3,1): ReceivePrepareMsg flips the executed bit of a row it did not write, per client
+FLOOR_C2_EXPAND = {a: 1000 for a in COUNTED_C2 if a not in (A_SendSV, A_ReceiveHigherDVC)}     # act_generated of the seeded level of (3,2,3,1) ...
+FLOOR_C2_EXPAND[A_SendSV] = 150                                     # ... (ReceiveHigherDVC is not floored there: 5 instances at L = 1)
 _cache = {}
 
 
+def walks_of(key):
+    return SPACES[key] if key in SPACES else SPACES_C2[key]
+
+
+def expected(key):
+    """the counted actions the space `key` must itself contribute to"""
+    return EXPECTED[key] if key in EXPECTED else COUNTED_C2
+
+
+def policy(key):
+    """keyword arguments of the policy a space runs under, the same for orc.Params, pyoracle.Model and Model.from_constants"""
+    return dict(assume_commit_number=True) if key in SPACES_C2 else {}
+
+
+def params(orc, key, **kw):
+    return orc.Params(*key, **dict(policy(key), **kw))
+
+
+def py_model(key, **kw):
+    from oracle import pyoracle as po
+    return po.Model(key[0], key[1], tuple("v%d" % (i + 1) for i in range(key[2])), key[3], **dict(policy(key), **kw))
+
+
+def product_model(vt, key, **kw):
+    return vt.Model.from_constants(R=key[0], C_=key[1], n=key[2], L=key[3], **dict(policy(key), **kw))
+
+
 def get(orc, key, kind, **kw):
-    """one walk of the space `key` = (R, C, n, L), kind "vc" or "st" (frozen = the last two replicas at R = 5, the last one at R = 4); cached per
-    process"""
+    """one walk of the space `key` = (R, C, n, L), kind "vc" or "st" (frozen = the last two replicas at R = 5, the last one at R = 4 and R = 3); cached
+    per process"""
     k = (key, kind, tuple(sorted(kw.items())), orc.fp_seed())
     if k not in _cache:
-        P = orc.Params(*key)
+        P = params(orc, key)
         if kind == "vc":
             _cache[k] = harvest_vc(orc, P, **kw)
         else:
-            _cache[k] = harvest_st(orc, P, frozen=(4, 5) if key[0] == 5 else (4,), **kw)
+            _cache[k] = harvest_st(orc, P, frozen=(4, 5) if key[0] == 5 else (key[0],), **kw)
     return _cache[k]
 
 
 def space(orc, key):
-    """the harvest of one space of SPACES: the union of its walks (one state per fingerprint); cached per process"""
+    """the harvest of one space of SPACES or SPACES_C2: the union of its walks (one state per fingerprint); cached per process"""
     k = (key, "space", orc.fp_seed())
     if k not in _cache:
         by_fp, vp = {}, set()
-        for kind, kw in SPACES[key]:
+        for kind, kw in walks_of(key):
             h = get(orc, key, kind, **kw)
             by_fp.update(zip(h.fps, h.records))
             vp.update(h.violating_parents)
-        _cache[k] = Harvest(orc, orc.Params(*key), by_fp, vp)
+        _cache[k] = Harvest(orc, params(orc, key), by_fp, vp)
     return _cache[k]
+
+
+def c2_facts(orc, key):
+    """what makes a two-client harvest a test of the ClientCount = 2 code, from the oracle's successors unpacked by oracle/pycodec.py alone (cached per
+    process).  A ReceivePrepareMsg instance "flips client c" when the executed bit of row c of the receiving replica's client table changes although the
+    appended entry is the OTHER client's: the row the else branch of VSR.tla:414-421 recomputes.
+      flip_states[c]    indices of the states with such an instance        flips[c]      such instances
+      both_rows         ReceivePrepareMsg instances that change both rows   exec_rows[c]  ExecuteOp instances that change row c"""
+    k = (key, "c2_facts", orc.fp_seed())
+    if k in _cache:
+        return _cache[k]
+    from oracle import pycodec
+    h, PM = space(orc, key), py_model(key)
+    assert key[1] == 2
+    out = dict(flip_states={1: [], 2: []}, flips={1: 0, 2: 0}, both_rows=0, exec_rows={1: 0, 2: 0})
+    for i in range(len(h)):
+        acts = h.actions(i)
+        if A_ReceivePrepareMsg not in acts and A_ExecuteOp not in acts:
+            continue
+        p = pycodec.unpack(PM, [int(x) for x in h.records[i]])
+        flipped = set()
+        for s in h.successors(i):
+            if s["action"] not in (A_ReceivePrepareMsg, A_ExecuteOp):
+                continue
+            c = pycodec.unpack(PM, [int(x) for x in s["words"]])
+            changed = [(r, cl) for r in range(key[0]) for cl in (1, 2) if p["rep_client_table"][r][cl - 1] != c["rep_client_table"][r][cl - 1]]
+            if s["action"] == A_ExecuteOp:
+                for _r, cl in changed:
+                    out["exec_rows"][cl] += 1
+                continue
+            (r,) = [r for r in range(key[0]) if len(c["rep_log"][r]) == len(p["rep_log"][r]) + 1]
+            other = 3 - dict(c["rep_log"][r][-1])["client_id"]
+            if len(changed) == 2:
+                out["both_rows"] += 1
+            if dict(p["rep_client_table"][r][other - 1])["executed"] != dict(c["rep_client_table"][r][other - 1])["executed"]:
+                out["flips"][other] += 1
+                flipped.add(other)
+        for cl in flipped:
+            out["flip_states"][cl].append(i)
+    _cache[k] = out
+    return out
+
+
+def c2_state_facts(orc, key):
+    """-> (states with a log that holds entries of both clients, states in which replica 1 holds a request, request_number > 0, of both clients)"""
+    from oracle import pycodec
+    h, PM = space(orc, key), py_model(key)
+    both_logs = both_requests = 0
+    for rec in h.records:
+        p = pycodec.unpack(PM, [int(x) for x in rec])
+        both_logs += any(len(set(dict(e)["client_id"] for e in lg)) == 2 for lg in p["rep_log"])
+        both_requests += all(dict(row)["request_number"] > 0 for row in p["rep_client_table"][0])
+    return both_logs, both_requests
+
+
+C2_PY_SAMPLE = 60
+
+
+def _stride(idx, k):
+    k = min(k, len(idx))
+    return [idx[(j * len(idx)) // k] for j in range(k)]
+
+
+def c2_py_sample(orc, key):
+    """indices of the states on which the Python restatement is compared: an even stride of 60 of the states that enable each counted action, and of the
+    states in which ReceivePrepareMsg flips a row of client 1 / of client 2 -> (sorted indices, {action or ("flip", client): states taken})"""
+    h, facts = space(orc, key), c2_facts(orc, key)
+    states_of = collections.defaultdict(list)
+    for i in range(len(h)):
+        for a in set(h.actions(i)):
+            if a in COUNTED_C2:
+                states_of[a].append(i)
+    for cl in (1, 2):
+        states_of[("flip", cl)] = facts["flip_states"][cl]
+    sample, taken = set(), {}
+    for what, idx in states_of.items():
+        mine = _stride(idx, C2_PY_SAMPLE)
+        taken[what] = len(mine)
+        sample.update(mine)
+    return sorted(sample), taken
 
 
 def max_bag_of_layout(P):

@@ -206,3 +206,132 @@ STEP = [
 SIM_STATE_MUST_HIT, SIM_STEP_MUST_HIT = "DvcHeld", "DvcGrew"
 
 text_of = wr.text_of
+
+
+# =====================================================================================================================
+# TWO CLIENTS: the sets of the two-client spaces (deep_harvest.SPACES_C2; three replicas, so the R >= 4 sets above do not apply).  What they read exists only in
+# a record of ClientCount = 2: the second row of a replica's client table (A-word bits of row 2; `\E c \in clients` unfolds to two rows; a client index that
+# is an expression becomes a select chain over two candidates), client_id = 2 inside log entries and inside the entry a PrepareMsg carries, the constant
+# ClientCount, and - in a pair - the row that ReceivePrepareMsg rewrites although the appended entry is the other client's (VSR.tla:414-421).
+# =====================================================================================================================
+def row(s, r, c):
+    return dict(s["rep_client_table"][r - 1][c - 1])
+
+
+def C_(s):
+    return len(s["rep_client_table"][0])
+
+
+def clients(s):
+    return range(1, C_(s) + 1)
+
+
+def client2_pending(s):
+    return any(row(s, r, 2)["request_number"] > 0 and not row(s, r, 2)["executed"] for r in reps(s))
+
+
+def later_client_later(s):
+    """the body differs between c = 1 and c = 2: client 2's request must sit at op number 2 or above"""
+    return all(row(s, 1, c)["request_number"] > 0 and row(s, 1, c)["op_number"] >= c for c in clients(s))
+
+
+def client2_committed(s):
+    return any(i + 1 <= s["rep_commit_number"][r - 1] and e["client_id"] == 2 for r in reps(s) for i, e in enumerate(wr.entries(s, r)))
+
+
+def msg_of_client2(s):
+    return any(n >= 1 and m["type"] == po.PrepareMsg and dict(m["message"])["client_id"] == 2 for m, n in msgs(s))
+
+
+def last_client_asked(s):
+    return C_(s) == 2 and row(s, R_(s), C_(s))["request_number"] > 0
+
+
+def rows_differ(s):
+    return any(row(s, r, 1)["executed"] != row(s, r, 2)["executed"] for r in reps(s))
+
+
+def row_of_prepare(s):
+    """a client index that is an expression: the row of the client whose entry a PrepareMsg carries, at the destination"""
+    return any(m["type"] == po.PrepareMsg and row(s, m["dest"], dict(m["message"])["client_id"])["op_number"] == m["op_number"] for m, n in msgs(s))
+
+
+STATE_C2 = [
+    ("Client2Pending", r"\E r \in replicas : rep_client_table[r][2].request_number > 0 /\ ~rep_client_table[r][2].executed", client2_pending),
+    ("LaterClientLater", r"\A c \in clients : rep_client_table[1][c].request_number > 0 /\ rep_client_table[1][c].op_number >= c", later_client_later),
+    ("Client2Committed", r"\E r \in replicas : \E i \in DOMAIN rep_log[r] : i <= rep_commit_number[r] /\ rep_log[r][i].client_id = 2", client2_committed),
+    ("MsgOfClient2", r"\E m \in DOMAIN messages : messages[m] >= 1 /\ m.message.client_id = 2", msg_of_client2),
+    ("LastClientAsked", r"ClientCount = 2 /\ rep_client_table[ReplicaCount][ClientCount].request_number > 0", last_client_asked),
+    ("RowsDiffer", r"\E r \in replicas : rep_client_table[r][1].executed # rep_client_table[r][2].executed", rows_differ),
+    ("RowOfPrepare", r"\E m \in DOMAIN messages : m.type = PrepareMsg /\ rep_client_table[m.dest][m.message.client_id].op_number = m.op_number", row_of_prepare),
+]
+
+
+def appended_entry_of(p, c, r, client):
+    """replica r's log has a position in the child that the parent's has not, and the entry there is `client`'s"""
+    return any(i >= len(p["rep_log"][r - 1]) and e["client_id"] == client for i, e in enumerate(wr.entries(c, r)))
+
+
+def other_row_rewritten(mine, other):
+    """the row of `other` differs at a replica whose log gained an entry of `mine`, under ReceivePrepareMsg: the row the else branch of VSR.tla:414-421 rewrites"""
+    return lambda p, c, a: a == "ReceivePrepareMsg" and any(row(c, r, other) != row(p, r, other) and appended_entry_of(p, c, r, mine) for r in reps(p))
+
+
+def row1_unchanged(p, c, a):
+    return all(row(c, r, 1) == row(p, r, 1) for r in reps(p))
+
+
+def executed_rose(p, c, a):
+    return any(row(c, r, cl)["executed"] and not row(p, r, cl)["executed"] for r in reps(p) for cl in clients(p))
+
+
+def executed_rises_only_on_execute_op(p, c, a):
+    """"the executed bit of either client rises only on ExecuteOp or ReceivePrepareMsg" is TRUE on every pair of these spaces (the bit rose on 133 + 120 sampled
+    pairs, all of them of those two actions), so it cannot take both verdicts.  This is the same implication with the second action left out: false exactly where
+    ReceivePrepareMsg raises a bit (90 and 84 sampled pairs), among them the rows the else branch of VSR.tla:414-421 recomputes."""
+    return (not executed_rose(p, c, a)) or a == "ExecuteOp"
+
+
+def last_client_entry_appended(p, c, a):
+    return any(appended_entry_of(p, c, r, C_(p)) for r in reps(p))
+
+
+def _other_row_text(mine, other):
+    t = "rep_client_table'[r][%d]" % other
+    u = "rep_client_table[r][%d]" % other
+    return (r"step_action = ReceivePrepareMsg /\ (\E r \in replicas : (%s.executed # %s.executed \/ %s.request_number # %s.request_number \/ %s.op_number # %s.op_number) "
+            r"/\ (\E i \in DOMAIN rep_log'[r] : ~(i \in DOMAIN rep_log[r]) /\ rep_log'[r][i].client_id = %d))" % (t, u, t, u, t, u, mine))
+
+
+STEP_C2 = [
+    ("Row2RewrittenByClient1", _other_row_text(1, 2), other_row_rewritten(1, 2)),
+    ("Row1RewrittenByClient2", _other_row_text(2, 1), other_row_rewritten(2, 1)),
+    ("Row1Unchanged", r"\A r \in replicas : UNCHANGED rep_client_table[r][1].request_number /\ UNCHANGED rep_client_table[r][1].op_number "
+                      r"/\ UNCHANGED rep_client_table[r][1].executed", row1_unchanged),
+    ("ExecutedRose", r"\E r \in replicas : \E c \in clients : rep_client_table[r][c].executed' /\ ~rep_client_table[r][c].executed", executed_rose),
+    ("ExecutedRisesOnlyOnExecuteOp", r"(\E r \in replicas : \E c \in clients : rep_client_table'[r][c].executed /\ ~rep_client_table[r][c].executed) "
+                                     r"=> step_action = ExecuteOp", executed_rises_only_on_execute_op),
+    ("LastClientEntryAppended", r"\E r \in replicas : \E i \in DOMAIN rep_log'[r] : ~(i \in DOMAIN rep_log[r]) /\ rep_log'[r][i].client_id = ClientCount",
+     last_client_entry_appended),
+]
+N_C2_FLIP_PARENTS = 75
+BOTH_VERDICTS = 20                                                  # every two-client predicate: true on at least 20 and false on at least 20 sampled items
+SIM_C2_STATE_MUST_HIT, SIM_C2_STEP_MUST_HIT = "Client2Pending", "LastClientEntryAppended"
+
+
+def c2_parent_indices(n, flip_states):
+    """the 150 sampled parents of a two-client harvest of n states: an even stride of 75, and an even stride of 75 of the states in which ReceivePrepareMsg flips
+    the executed bit of a row it did not write (deep_harvest.c2_facts: flip_states of client 1 and 2 together) - an even stride of the harvest alone holds about
+    six such pairs"""
+    first = [(k * n) // (N_PARENTS - N_C2_FLIP_PARENTS) for k in range(N_PARENTS - N_C2_FLIP_PARENTS)]
+    rest = sorted(set(flip_states) - set(first))
+    return sorted(first + [rest[(k * len(rest)) // N_C2_FLIP_PARENTS] for k in range(N_C2_FLIP_PARENTS)])
+
+
+def state_sets(key):
+    """(tag, predicates) of the state sets of a space"""
+    return (("A", wr.SET_A), ("B", wr.set_b(key[3])), ("C2", STATE_C2) if key[1] == 2 else ("R4", STATE))
+
+
+def step_sets(key):
+    return (("A", sr.SET_A), ("B", sr.SET_B), ("C", sr.SET_C), ("C2", STEP_C2) if key[1] == 2 else ("R4", STEP))

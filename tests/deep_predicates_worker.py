@@ -5,7 +5,12 @@ Runs with VSRMC_LIB = libvsrmc_hooks.so (ModelChecker.seed_records, csrc/host_te
 function here: this process only reports — figures to out.json, the parents' level as the checker stores it (the bag order of a stored record names the
 ordinals) to frontier.npz.  The parent process compares everything with the reference.
 
-usage: deep_predicates_worker.py R C n L seeds.npz out.json frontier.npz"""
+With `deep` (the two-client spaces) a third seed set — a few of the parents — is seeded, the last state set and the last step set are attached (deep_attach) and
+two deepen() passes run: the first inserts level 2 into the seen-set only; the second regenerates level 2, inserts level 3 and probes level 4 (k_probe_where).
+Every result of deep_results() is reported with its lists (deep_where_states, deep_step_pairs as parent fingerprint and bits).
+
+usage: deep_predicates_worker.py R C n L seeds.npz out.json frontier.npz [assume_commit_number] [deep]
+    assume_commit_number    the policy of the two-client spaces, for Model.from_constants"""
 import json
 import os
 import sys
@@ -18,22 +23,44 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 
-def sets_of(L):
-    """(tag, predicates) of the state sets and of the step sets: the texts are what this process needs of them"""
+def sets_of(key):
+    """(tag, predicates) of the state sets and of the step sets of a space: the texts are what this process needs of them"""
     import deep_predicates_reference as dp
-    import step_reference as sr
-    import where_reference as wr
-    return ((("A", wr.SET_A), ("B", wr.set_b(L)), ("R4", dp.STATE)), (("A", sr.SET_A), ("B", sr.SET_B), ("C", sr.SET_C), ("R4", dp.STEP)))
+    return dp.state_sets(key), dp.step_sets(key)
+
+
+def deep_passes(m, mc, wr, state_set, step_set, words, off):
+    mc.seed_records(words, off)
+    ws, wp = m.compile_where(wr.text_of(state_set[1])), m.compile_step(wr.text_of(step_set[1]))
+    mc.deep_attach(ws, wp)
+    out, listed = dict(passes=[], results=[]), set()
+    for _ in range(2):
+        a, b = mc.deepen()
+        out["passes"].append(dict(inserted={k: a[k] for k in ("level", "n_new", "generated", "viol_mask")}, probed=None if b is None else b["level"]))
+        for r in mc.deep_results():
+            k = (r["level"], r["kind"])
+            if k in listed:
+                continue
+            listed.add(k)
+            fps, bits = mc.deep_where_states(r["level"], probed=r["kind"] == "probed")
+            r["states"] = [[int(x), int(y)] for x, y in zip(fps, bits)]
+            if r["step"] is not None:
+                pf, _po, pb = mc.deep_step_pairs(r["level"])
+                r["pairs"] = sorted([int(x), int(y)] for x, y in zip(pf, pb))
+            out["results"].append(r)
+    return out
 
 
 def main():
     R, C_, n, L = (int(x) for x in sys.argv[1:5])
+    flags = set(sys.argv[8:])
+    policy = dict(assume_commit_number=True) if "assume_commit_number" in flags else {}
     z = np.load(sys.argv[5])
     import vsr_tlaplus_amd as vt
     import where_reference as wr
     assert getattr(vt.load(), "vsrmc_test_checker_seed_records", None) is not None, "run me with VSRMC_LIB = libvsrmc_hooks.so"
-    state_sets, step_sets = sets_of(L)
-    m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L)
+    state_sets, step_sets = sets_of((R, C_, n, L))
+    m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L, **policy)
     mc = vt.ModelChecker(m, table_log2=20, frontier_words=1 << 22, frontier_states=1 << 17, pending_entries=1 << 17)
     out = dict(where={}, step={})
     mc.seed_records(z["words"], z["off"])
@@ -54,6 +81,8 @@ def main():
         out["step"][tag] = dict({k: t[k] for k in ("level", "n_states", "n_pairs", "n_err", "count", "min_fp", "min_index", "min_ordinal", "min_action")},
                                 found_at=[None if fp is None else mc.find_fp(fp) for fp in t["min_fp"]],
                                 pairs=[[int(a), int(b), int(c)] for a, b, c in zip(fps, ords, bits)])
+    if "deep" in flags:
+        out["deep"] = deep_passes(m, mc, wr, state_sets[-1], step_sets[-1], z["dwords"], z["doff"])
     mc.close()
     m.close()
     with open(sys.argv[6], "w") as f:

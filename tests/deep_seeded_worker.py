@@ -15,7 +15,10 @@ design (VSRMC_E_STATE).  The oracle decides: a set whose image has such fingerpr
 that differs) and every part is stepped on its own; seeds that still produce one are left out of that run (at most 1 %, printed).  exact_ties = 1 takes
 the whole set and must resolve every such fingerprint to the smallest auxkey.
 
-usage: deep_seeded_worker.py R C n L seeds.npz out.json [full | viol | small]
+usage: deep_seeded_worker.py R C n L seeds.npz out.json [full | viol | small | c2] [assume_commit_number] [generous]
+    full, viol, small, c2   what runs besides the two stored steps (main)
+    assume_commit_number    the policy of the two-client spaces, for the oracle's Params and for Model.from_constants alike
+    generous                the buffers of test_a_tile_that_overflows_the_work_list_is_taken_again_in_pieces (for a run under VSRMC_CCAP)
 """
 import collections
 import json
@@ -48,10 +51,11 @@ class Case:
     view hash per record) and `verdict(words, inv_mask)` gives the oracle's verdict on a record where orc.invariants alone does not (an evaluation error
     that the kernels report as a violation)."""
 
-    def __init__(self, orc, key, recs, succ, inv_mask=1, make_model=None, verdict=None):
+    def __init__(self, orc, key, recs, succ, inv_mask=1, make_model=None, verdict=None, policy=None):
         self.orc, self.key, self.recs, self.succ = orc, key, recs, succ
         self.inv_mask, self.make_model, self.verdict = inv_mask, make_model, verdict
-        self.P = orc.Params(*key, invariant_mask=inv_mask)
+        self.policy = dict(policy or {})                            # e.g. assume_commit_number=True: the oracle's Params and the product's model alike
+        self.P = orc.Params(*key, invariant_mask=inv_mask, **self.policy)
         self.fps = [orc.fingerprint(self.P, r)[0] for r in recs]
         assert len(set(self.fps)) == len(recs), "the seeds are distinct states"
         seed_fp = set(self.fps)
@@ -98,16 +102,20 @@ class Case:
         return tuple(int(x) for x in self.orc.normalise(self.P, words))
 
 
-def make_checker(vt, case, exact, frontier_words=None):
+def make_checker(vt, case, exact, frontier_words=None, generous=False):
+    """generous: the buffers of test_a_tile_that_overflows_the_work_list_is_taken_again_in_pieces (every re-launch leaves partly used chunks behind)"""
     if case.make_model:
         m = case.make_model(vt, int(case.P.arr[7]))
     else:
         R, C_, n, L = case.key
-        m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L, invariant_mask=int(case.P.arr[7]))
+        m = vt.Model.from_constants(R=R, C_=C_, n=n, L=L, invariant_mask=int(case.P.arr[7]), **case.policy)
     fw = frontier_words or _pow2_at_least(max(1 << 24, 2 * max(case.new_words_dev, case.seed_words_dev)))
     fs = _pow2_at_least(max(1 << 16, 4 * max(len(case.new), len(case.recs))))
-    mc = vt.ModelChecker(m, table_log2=23, frontier_words=fw, frontier_states=fs, pending_entries=1 << 22 if exact else 1 << 16,
-                         exact_ties=bool(exact))
+    if generous:
+        mc = vt.ModelChecker(m, table_log2=22, frontier_words=1 << 26, frontier_states=1 << 22, pending_entries=1 << 21, exact_ties=bool(exact))
+    else:
+        mc = vt.ModelChecker(m, table_log2=23, frontier_words=fw, frontier_states=fs, pending_entries=1 << 22 if exact else 1 << 16,
+                             exact_ties=bool(exact))
     return m, mc
 
 
@@ -168,21 +176,23 @@ def check_level(vt, case, mc, d, label, n_traces=48):
     return len(sample)
 
 
-def run_step(vt, orc, key, recs, succ, exact, inv_mask=1, label="", **model_kw):
+def run_step(vt, orc, key, recs, succ, exact, inv_mask=1, label="", generous=False, **model_kw):
     case = Case(orc, key, recs, succ, inv_mask, **model_kw)
-    m, mc = make_checker(vt, case, exact)
+    m, mc = make_checker(vt, case, exact, generous=generous)
     try:
         mc.seed_records(*case.batch())
         assert np.array_equal(mc.level_fps(), np.array(sorted(case.fps), dtype=np.uint64)), label
+        before = mc.extra_launches()
         t0 = time.time()
         d = mc.step()
         dt = time.time() - t0
+        redo = mc.extra_launches() - before                           # lists of overflowed tiles launched again (k_expand: s_over, redo_overflowed_tiles)
         n_tr = check_level(vt, case, mc, d, label)
     finally:
         mc.close()
         m.close()
     return dict(label=label, seeds=len(recs), generated=case.generated, n_new=len(case.new), ties=len(case.ties), violators=len(case.viol),
-                act_generated=case.act, traces=n_tr, step_seconds=dt, expand_ms=d["expand_ms"])
+                act_generated=case.act, traces=n_tr, step_seconds=dt, expand_ms=d["expand_ms"], redo_launches=redo)
 
 
 def parts_without_ties(orc, key, recs, succ, **model_kw):
@@ -293,37 +303,126 @@ def extras_512(vt, orc, key, recs, succ, out):
         m.close()
 
 
+def _xor_sum(fps):
+    x = s_ = 0
+    for f in fps:
+        x ^= f
+        s_ = (s_ + f) & M64
+    return x, s_
+
+
+def extras_c2(vt, orc, key, recs, succ, out, policy):
+    """the rest of the family at two clients (SPEC 323 at (3,2,3,L), generic at (3,2,2,1)): probe, terminal scan, select, two passes beyond the record
+    buffers — the first inserts level 2 into the seen-set only, the second regenerates it from the seeds and inserts level 3"""
+    from deep_harvest import COUNTED_C2
+    case = Case(orc, key, recs, succ, policy=policy)
+    assert not case.ties
+    words, off = case.batch()
+    m, mc = make_checker(vt, case, 0)
+    try:
+        mc.seed_records(words, off)
+        p = mc.probe()
+        assert p["generated"] == case.generated and p["viol_mask"] == 0, (p["generated"], case.generated)
+        assert mc.probe_violators() == []
+        mc.seed_records(words, off)
+        t = mc.terminal_scan()
+        assert (t["level"], t["n_states"], t["n_terminal"]) == (1, len(recs), len(case.deadlocks)), t
+        assert t["min_fp"] == (min(case.deadlocks) if case.deadlocks else None)
+        for a in COUNTED_C2:
+            _w, _o, n_match = mc.select(1 << a, 16)
+            assert n_match == case.enabled[a], (vt.ACTION_NAMES[a], n_match, case.enabled[a])
+        out["terminal"] = len(case.deadlocks)
+        out["select"] = {vt.ACTION_NAMES[a]: case.enabled[a] for a in COUNTED_C2}
+    finally:
+        mc.close()
+        m.close()
+    # the probe of an image that violates: the same seeds under invariant mask 3 (AcknowledgedWritesExistOnMajority, VSR.tla:937-943)
+    case3 = Case(orc, key, recs, succ, inv_mask=3, policy=policy)
+    assert case3.viol, "no violating successor under mask 3: the violation checks would be vacuous"
+    m, mc = make_checker(vt, case3, 0)
+    try:
+        mc.seed_records(*case3.batch())
+        p = mc.probe()
+        vmask = 0
+        for v in case3.viol.values():
+            vmask |= v
+        assert (p["generated"], p["viol_fp"], p["viol_mask"]) == (case3.generated, min(case3.viol), vmask), p
+        assert mc.probe_violators() == sorted(case3.viol)
+        out["probe_violators"] = len(case3.viol)
+    finally:
+        mc.close()
+        m.close()
+    # level 3 by the oracle: the successors of level 2 that are neither seeds nor of level 2
+    known = set(case.fps) | set(case.new)
+    gen3, act3, new3, viol3 = 0, [0] * 16, {}, 0
+    perms = 1
+    for k in range(2, key[2] + 1):
+        perms *= k
+    for f in case.new:
+        for s in orc.successors(case.P, case.by_fp[f][0][2]["words"]):
+            gen3 += 1
+            act3[s["action"]] += 1
+            if s["fp"] not in known:
+                new3.setdefault(s["fp"], (set(), len(s["words"]) + perms))[0].add(s["auxkey"])
+                viol3 |= s["inv"]
+    assert all(len(aks) == 1 for aks, _n in new3.values()), "level 3 holds one fingerprint under two auxkeys"
+    words3 = sum(n for _aks, n in new3.values())
+    fw = _pow2_at_least(case.seed_words_dev)
+    assert max(case.new_words_dev, words3) > fw, "the record buffers of this run must be too small for a level it passes"
+    m, mc = make_checker(vt, case, 0, frontier_words=fw)
+    try:
+        mc.seed_records(words, off)
+        a, b = mc.deepen()
+        got = (a["level"], a["n_new"], a["generated"], list(a["act_generated"]), a["fp_xor"], a["fp_sum"], a["viol_mask"])
+        assert got == (2, len(case.new), case.generated, case.act) + _xor_sum(case.new) + (0,), (got[:3], len(case.new), case.generated)
+        assert b is None or (b["level"], b["generated"], b["viol_mask"]) == (3, gen3, viol3), b      # (a probed level generates what it generates when it is inserted)
+        a, b = mc.deepen()
+        got = (a["level"], a["n_new"], a["generated"], list(a["act_generated"]), a["fp_xor"], a["fp_sum"], a["viol_mask"])
+        assert got == (3, len(new3), gen3, act3) + _xor_sum(new3) + (viol3,), (got[:3], len(new3), gen3)
+        assert a["distinct"] == len(recs) + len(case.new) + len(new3)
+        out["deepen"] = dict(frontier_words=fw, level2_words=case.new_words_dev, level3_words=words3, n_new=[len(case.new), len(new3)], generated=[case.generated, gen3],
+                             act_generated3=act3)
+    finally:
+        mc.close()
+        m.close()
+
+
 def main():
+    flags = set(sys.argv[7:])
+    generous = "generous" in flags
+    policy = dict(assume_commit_number=True) if "assume_commit_number" in flags else {}
     key = tuple(int(x) for x in sys.argv[1:5])
     z = np.load(sys.argv[5])
     out_path = sys.argv[6]
-    full = len(sys.argv) > 7 and sys.argv[7] == "full"                # SPEC 512: the whole family
-    viol = full or (len(sys.argv) > 7 and sys.argv[7] == "viol")     # a stored step whose image violates (invariant mask 3)
+    full = "full" in flags                                            # SPEC 512: the whole family
+    viol = full or "viol" in flags or "c2" in flags                   # a stored step whose image violates (invariant mask 3)
     import vsr_tlaplus_amd as vt
     from oracle import orc
     assert getattr(vt.load(), "vsrmc_test_checker_seed_records", None) is not None, "run me with VSRMC_LIB = libvsrmc_hooks.so"
     words, off = z["words"], z["off"]
     recs = [words[int(off[i]): int(off[i + 1])].copy() for i in range(len(off) - 1)]
-    P = orc.Params(*key)
+    P = orc.Params(*key, **policy)
     succ = [orc.successors(P, r) for r in recs]
     out = dict(key=list(key), seeds=len(recs), runs=[])
-    parts, left = parts_without_ties(orc, key, recs, succ)
+    parts, left = parts_without_ties(orc, key, recs, succ, policy=policy)
     assert left * 100 <= len(recs), ("more than 1 % of the seeds left out of the single-pass run", left, len(recs))
     print("seeds %d, parts %s, left out of the single-pass run %d" % (len(recs), [len(p) for p in parts], left), flush=True)
     out["left_out"], out["parts"] = left, [len(p) for p in parts]
-    small = len(sys.argv) > 7 and sys.argv[7] == "small"            # hand-built records among a few harvested ones
+    small = "small" in flags                                        # hand-built records among a few harvested ones
     assert small or max(len(p) for p in parts) >= 4096
     for k, part in enumerate(parts):
-        out["runs"].append(run_step(vt, orc, key, [recs[i] for i in part], [succ[i] for i in part], 0, label="exact_ties=0 part %d" % k))
+        out["runs"].append(run_step(vt, orc, key, [recs[i] for i in part], [succ[i] for i in part], 0, label="exact_ties=0 part %d" % k, policy=policy, generous=generous))
         print(json.dumps(out["runs"][-1]), flush=True)
-    out["runs"].append(run_step(vt, orc, key, recs, succ, 1, label="exact_ties=1"))
+    out["runs"].append(run_step(vt, orc, key, recs, succ, 1, label="exact_ties=1", policy=policy, generous=generous))
     print(json.dumps(out["runs"][-1]), flush=True)
     if viol:
-        out["runs"].append(run_step(vt, orc, key, recs, succ, 0, inv_mask=3, label="exact_ties=0 mask 3"))
+        out["runs"].append(run_step(vt, orc, key, recs, succ, 0, inv_mask=3, label="exact_ties=0 mask 3", policy=policy))
         assert out["runs"][-1]["violators"] > 0
         print(json.dumps(out["runs"][-1]), flush=True)
     if full:
         extras_512(vt, orc, key, recs, succ, out)
+    if "c2" in flags:
+        extras_c2(vt, orc, key, recs, succ, out, policy)
     with open(out_path, "w") as f:
         json.dump(out, f)
     print("ok", flush=True)

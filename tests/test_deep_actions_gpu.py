@@ -54,15 +54,20 @@ def _norm(orc, P, words):
 _leg_a = {}
 
 
-def _three_ways(vt, orc, key):
-    """leg A over one space -> instances per action (memoised: the floor test needs every space)"""
+def _three_ways(vt, orc, key, py_sample=None):
+    """leg A over one space of deep_harvest.SPACES or SPACES_C2 (under the policy of that space) -> instances per action (memoised: the floor test needs
+    every space).  py_sample: the indices of the states on which the Python restatement is compared; None: the first 60 states that enable each expected
+    action"""
     if key in _leg_a:
         return _leg_a[key]
     from oracle import pycodec, pyoracle as po
     h = dh.space(orc, key)
     P = h.P
-    PM = po.Model(key[0], key[1], tuple("v%d" % (i + 1) for i in range(key[2])), key[3])
-    m = vt.Model.from_constants(R=key[0], C_=key[1], n=key[2], L=key[3])
+    PM = dh.py_model(key)
+    m = dh.product_model(vt, key)
+    expected = dh.expected(key)
+    py_set = None if py_sample is None else set(py_sample)
+    n_py = 0
     inst = collections.Counter()
     py_checked = collections.Counter()
     n_states = 0
@@ -88,8 +93,9 @@ def _three_ways(vt, orc, key):
             for x in osucc[k]:
                 inst[x["action"]] += 1
                 enabled.add(x["action"])
-            want_py = [a for a in dh.EXPECTED[key] if a in enabled and py_checked[a] < 60]
+            want_py = [a for a in expected if a in enabled and py_checked[a] < 60] if py_set is None else i in py_set
             if want_py:                                             # the independent Python restatement on a sample
+                n_py += 1
                 st = pycodec.unpack(PM, [int(x) for x in h.records[i]])
                 ps = sorted((nm, tuple(pycodec.normalise(PM, pycodec.pack(PM, t)))) for nm, t in po.successors(PM, st))
                 cs = sorted((vt.ACTION_NAMES[x["action"]], tuple(pycodec.normalise(PM, [int(v) for v in x["words"]]))) for x in osucc[k])
@@ -98,9 +104,12 @@ def _three_ways(vt, orc, key):
                     py_checked[a] += 1
     m.close()
     assert n_states == len(h)                                       # the share of harvested states left out of the comparison is zero
-    for a in dh.EXPECTED[key]:
-        assert py_checked[a] >= 60, (key, vt.ACTION_NAMES[a], py_checked[a])
-    print(key, "states", n_states, {vt.ACTION_NAMES[a]: inst[a] for a in sorted(inst)})
+    if py_set is None:
+        for a in expected:
+            assert py_checked[a] >= 60, (key, vt.ACTION_NAMES[a], py_checked[a])
+    else:
+        assert n_py == len(py_set)                                  # ... and so is the share of the sample
+    print(key, "states", n_states, "of them through the Python restatement", n_py, {vt.ACTION_NAMES[a]: inst[a] for a in sorted(inst)})
     _leg_a[key] = inst
     return inst
 
@@ -128,24 +137,27 @@ def test_k_successors_instances_reach_the_floors(vt, orc):
 _leg_b = {}
 
 
-def _seeded(orc, key, tmp):
-    if key in _leg_b:
-        return _leg_b[key]
+def _seeded(orc, key, tmp, mode=None, env=None, tag=""):
+    """the harvest of one space seeded as level 1 of a checker in a child process (tests/deep_seeded_worker.py) -> what the worker reports.  mode: the
+    worker's mode and policy arguments; env: more environment of the child; tag: what tells two runs of one space apart"""
+    if (key, tag) in _leg_b:
+        return _leg_b[(key, tag)]
     h = dh.space(orc, key)
     words, off = h.batch(0, len(h))
     seeds = os.path.join(str(tmp), "seeds_%d%d%d%d.npz" % key)
-    out = os.path.join(str(tmp), "seeded_%d%d%d%d.json" % key)
+    out = os.path.join(str(tmp), "seeded_%d%d%d%d%s.json" % (key + (tag,)))
     np.savez(seeds, words=words, off=off)
     hooks = os.path.join(ROOT, "vsr_tlaplus_amd", "libvsrmc_hooks.so")
     assert os.path.exists(hooks), "build it: python vsr_tlaplus_amd/build.py"
-    mode = {(5, 1, 2, 1): ["full"], (4, 1, 2, 1): ["viol"]}.get(key, [])
+    if mode is None:
+        mode = {(5, 1, 2, 1): ["full"], (4, 1, 2, 1): ["viol"]}.get(key, [])
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "deep_seeded_worker.py")] + [str(x) for x in key] + [seeds, out] + mode,
-                       capture_output=True, text=True, timeout=1500, env=dict(os.environ, VSRMC_LIB=hooks))
+                       capture_output=True, text=True, timeout=1500, env=dict(os.environ, VSRMC_LIB=hooks, **(env or {})))
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
     with open(out) as f:
-        _leg_b[key] = json.load(f)
-    return _leg_b[key]
+        _leg_b[(key, tag)] = json.load(f)
+    return _leg_b[(key, tag)]
 
 
 def _act(res, exact):

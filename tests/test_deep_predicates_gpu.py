@@ -7,7 +7,15 @@ harvest of tests/deep_harvest.py (deep_predicates_reference.py: 1500 states and 
 pinned by test_deep_predicates_cpu.py) and on the hand-built records of deep_harvest.hand_built.  Every comparison is exact, against hand-written Python
 functions over pycodec's unpack of the CPU oracle's records (where_reference.py, step_reference.py, deep_predicates_reference.py — never the parser).
 
-The level scans run in a child process under libvsrmc_hooks.so (tests/deep_predicates_worker.py): the sample is seeded as level 1 of a checker."""
+The level scans run in a child process under libvsrmc_hooks.so (tests/deep_predicates_worker.py): the sample is seeded as level 1 of a checker.
+
+TWO CLIENTS: the same tests run on (3,2,3,1) and (3,2,2,1) of deep_harvest.SPACES_C2 under the policy assume_commit_number, with the two-client sets of
+deep_predicates_reference.py (tag C2) in the place of the R >= 4 sets: the second row of a client table, "exists c in clients", a client index that is an expression,
+client_id = 2 in logs and in the entry a PrepareMsg carries, ClientCount, and the row ReceivePrepareMsg rewrites for the client whose entry it did NOT append.  Half of
+the 150 parents there are states in which that happens (deep_predicates_reference.c2_parent_indices).  Every two-client predicate takes each verdict at least 20
+times on what is compared (pinned on the CPU by test_two_clients_cpu.py).  On these spaces the seeded child also runs two passes beyond the record buffers
+with the C2 sets attached: the inserted and regenerated levels (k_where / k_step_list on scratch slices) and the probed level (k_probe_where) against the
+oracle's levels through the Python predicates."""
 import collections
 import json
 import os
@@ -25,8 +33,10 @@ import where_reference as wr
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SPACES = sorted(dh.SPACES)
+C2_SPACES = [(3, 2, 3, 1), (3, 2, 2, 1)]
+SPACES = sorted(dh.SPACES) + C2_SPACES
 IDS = ["%d-%d-%d-%d" % k for k in SPACES]
+N_DEEP = 40                                                         # parents seeded for the passes beyond the record buffers (two-client spaces)
 Sample = collections.namedtuple("Sample", "key P PM fixed recs fps states words off precs pfps pstates pwords poff succ")
 
 
@@ -51,16 +61,8 @@ def _batch(recs):
     return np.concatenate(recs), np.cumsum([0] + [len(r) for r in recs]).astype(np.uint64)
 
 
-def _pm(key):
-    from oracle import pyoracle as po
-    return po.Model(key[0], key[1], tuple("v%d" % (i + 1) for i in range(key[2])), key[3])
-
-
-def _state_sets(key):
-    return (("A", wr.SET_A), ("B", wr.set_b(key[3])), ("R4", dp.STATE))
-
-
-STEP_SETS = (("A", sr.SET_A), ("B", sr.SET_B), ("C", sr.SET_C), ("R4", dp.STEP))
+_pm = dh.py_model
+_state_sets = dp.state_sets
 _samples = {}
 _views = {}                                                         # (key, normalised record) -> Python view
 _step_bits = {}                                                     # (key, tag, parent, child, action name) -> bits by the reference
@@ -87,21 +89,33 @@ def _sample(vt, orc, key):
     if key not in _samples:
         h = dh.space(orc, key)
         fixed = h.P.fixed_words()
-        si, pi = dp.state_indices(len(h)), dp.parent_indices(len(h))
-        assert len(set(si)) == dp.N_STATES and si[::10] == pi
+        si = dp.state_indices(len(h))
+        if key[1] == 2:
+            flips = dh.c2_facts(orc, key)["flip_states"]
+            pi = dp.c2_parent_indices(len(h), flips[1] + flips[2])
+            assert len(set(si)) == dp.N_STATES and len(set(pi)) == dp.N_PARENTS
+        else:
+            pi = dp.parent_indices(len(h))
+            assert len(set(si)) == dp.N_STATES and si[::10] == pi
         recs = [h.records[i] for i in si]
         states = [_view(key, _norm(fixed, r)) for r in recs]
         precs = [h.records[i] for i in pi]
         succ = [[(vt.ACTION_NAMES[s["action"]], _norm(fixed, s["words"])) for s in h.successors(i)] for i in pi]
         words, off = _batch(recs)
         pwords, poff = _batch(precs)
-        _samples[key] = Sample(key, h.P, _pm(key), fixed, recs, [h.fps[i] for i in si], states, words, off, precs, [h.fps[i] for i in pi], states[::10], pwords, poff,
-                               succ)
+        _samples[key] = Sample(key, h.P, _pm(key), fixed, recs, [h.fps[i] for i in si], states, words, off, precs, [h.fps[i] for i in pi],
+                               [_view(key, _norm(fixed, r)) for r in precs], pwords, poff, succ)
     return _samples[key]
 
 
 def _model(vt, key):
-    return vt.Model.from_constants(R=key[0], C_=key[1], n=key[2], L=key[3])
+    return dh.product_model(vt, key)
+
+
+def _both_verdicts(hits, n, label):
+    """every two-client predicate: true on at least 20 and false on at least 20 of the n items compared"""
+    for name, k in hits.items():
+        assert dp.BOTH_VERDICTS <= k <= n - dp.BOTH_VERDICTS, (label, name, k, n)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -131,6 +145,9 @@ def test_where_flags_on_the_sampled_states(vt, orc, key):
     hits = _flags_equal_the_reference(m, key, _state_sets(key), S.words, S.off, S.states, key)
     m.close()
     print("where_flags %s, hits of %d states: %s" % (key, len(S.states), hits))
+    if key[1] == 2:
+        _both_verdicts(hits["C2"], len(S.states), key)
+        return
     for name in ("DvcHeld", "DvcQuorum", "DvcAllButOne", "SvcFour", "TailView"):      # (both verdicts per replica count: test_deep_predicates_cpu.py)
         assert 0 < hits["R4"][name] < len(S.states), name
 
@@ -159,7 +176,7 @@ def test_random_expressions_on_a_sub_stride(vt, orc, key):
     m.close()
     used = sum(1 for k in range(100) if 0 < n_true[k] < len(states))
     print("random expressions: %d of 100 have both verdicts on %d states of %s" % (used, len(states), key))
-    assert used >= 30                                                # (the floor of test_where_gpu.py; by the reference alone 37, 61, 38 and 54 of them do here)
+    assert used >= 30                                                # (the floor of test_where_gpu.py; by the reference alone 37, 61, 38 and 54 of them do here, 68 and 64 at the two two-client spaces)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -171,7 +188,7 @@ def _step_flags_equal_the_reference(vt, m, key, fixed, words, off, parents, succ
     nx = m.get_next_states(words, off, cap_succ=max(64, 64 * len(parents)))
     assert len(nx) == sum(len(x) for x in succ), label
     hits = {}
-    for tag, preds in STEP_SETS:
+    for tag, preds in dp.step_sets(key):
         w = m.compile_step(sr.text_of(preds))
         assert w.names == [p[0] for p in preds] and w.step
         rows = m.step_flags(w, words, off)
@@ -207,6 +224,10 @@ def test_step_flags_on_the_sampled_parents(vt, orc, key):
     print("step_flags %s: %d pairs of %d parents, by action %s" % (key, n_pairs, len(parents), dict(by_action)))
     print("step_flags %s: pairs whose fourth block word changes %d, bag entries appended %s" % (key, word3, sorted(growth.items())))
     print("step_flags %s, hits: %s" % (key, hits))
+    if key[1] == 2:
+        _both_verdicts(hits["C2"], n_pairs, key)
+        assert by_action["ReceivePrepareMsg"] >= dp.N_C2_FLIP_PARENTS
+        return
     fl = dp.floors(key)
     assert word3 >= fl["word3"] and growth[key[0] - 1] >= fl["bcast"]
     assert hits["R4"]["DvcGrew"] > 0 and hits["R4"]["NewKeyForLast"] > 0 and hits["R4"]["DvcQuorumReached"] > 0
@@ -243,10 +264,12 @@ def test_hand_built_records_through_both(vt, orc, R):
 def test_scans_on_the_seeded_level(vt, orc, key, tmp_path):
     S = _sample(vt, orc, key)
     seeds, out, frontier = (os.path.join(str(tmp_path), x) for x in ("seeds.npz", "out.json", "frontier.npz"))
-    np.savez(seeds, words=S.words, off=S.off, pwords=S.pwords, poff=S.poff)
+    dwords, doff = _batch(S.precs[:N_DEEP])
+    np.savez(seeds, words=S.words, off=S.off, pwords=S.pwords, poff=S.poff, dwords=dwords, doff=doff)
     hooks = os.path.join(ROOT, "vsr_tlaplus_amd", "libvsrmc_hooks.so")
     assert os.path.exists(hooks), "build it: python vsr_tlaplus_amd/build.py"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "deep_predicates_worker.py")] + [str(x) for x in key] + [seeds, out, frontier],
+    more = ["assume_commit_number", "deep"] if key[1] == 2 else []
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "deep_predicates_worker.py")] + [str(x) for x in key] + [seeds, out, frontier] + more,
                        capture_output=True, text=True, timeout=300, env=dict(os.environ, VSRMC_LIB=hooks))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
     with open(out) as f:
@@ -278,7 +301,7 @@ def test_scans_on_the_seeded_level(vt, orc, key, tmp_path):
     nx = m.get_next_states(fwords, foff, cap_succ=max(64, 64 * len(frecs)))
     m.close()
     assert len(nx) == n_succ
-    for tag, preds in STEP_SETS:
+    for tag, preds in dp.step_sets(key):
         t = res["step"][tag]
         assert (t["level"], t["n_states"], t["n_err"]) == (1, len(frecs), 0), tag
         assert t["n_pairs"] + t["n_err"] == n_succ, tag              # the oracle's successor count
@@ -301,3 +324,59 @@ def test_scans_on_the_seeded_level(vt, orc, key, tmp_path):
             else:
                 assert t["min_fp"][k] is None and t["min_ordinal"][k] is None and t["min_action"][k] is None, (tag, preds[k][0])
         print("step_scan %s %s: %d pairs, %s" % (key, tag, t["n_pairs"], dict(zip((p[0] for p in preds), t["count"]))))
+    if key[1] == 2:
+        _check_the_passes_beyond_the_buffers(orc, S, res["deep"])
+
+
+def _check_the_passes_beyond_the_buffers(orc, S, deep):
+    """the first N_DEEP parents seeded as level 1, the C2 sets attached, two deepen() passes: levels 2 and 3 are scanned as regenerated / inserted levels (state
+    and step program), level 4 as the probed level (k_probe_where, the state program).  The levels are the oracle's: level k + 1 = the successors of level k
+    that no earlier level holds.  No C2 predicate reads an aux variable or names a value: every copy of a state has the same bits."""
+    key = S.key
+    state_preds, step_preds = dp.state_sets(key)[-1][1], dp.step_sets(key)[-1][1]
+    levels = {1: {int(orc.fingerprint(S.P, r)[0]): r for r in S.precs[:N_DEEP]}}
+    succ_of = {}
+    known = set(levels[1])
+    for lvl in (2, 3, 4):
+        nxt = {}
+        for fp, rec in levels[lvl - 1].items():
+            succ_of[fp] = orc.successors(S.P, rec)
+            for s in succ_of[fp]:
+                if s["fp"] not in known and s["fp"] not in nxt:
+                    nxt[s["fp"]] = s["words"]
+        known.update(nxt)
+        levels[lvl] = nxt
+    assert [(p["inserted"]["level"], p["inserted"]["n_new"], p["inserted"]["viol_mask"]) for p in deep["passes"]] == [(2, len(levels[2]), 0), (3, len(levels[3]), 0)]
+    assert deep["passes"][1]["inserted"]["generated"] == sum(len(succ_of[fp]) for fp in levels[2])
+    seen = {}
+    for r in deep["results"]:
+        probed = r["kind"] == "probed"
+        assert (r["level"], probed) not in seen and r["exact"] is True
+        seen[(r["level"], probed)] = r
+        lv = levels[r["level"]]
+        want = sorted((fp, wr.bits_of(state_preds, _view(key, _norm(S.fixed, rec)))) for fp, rec in lv.items())
+        hit = [x for x in want if x[1]]
+        assert [tuple(x) for x in r["states"]] == hit and r["n_hit_states"] == len(hit), (r["level"], r["kind"])
+        for k in range(len(state_preds)):
+            mine = [fp for fp, b in want if (b >> k) & 1]
+            assert (r["state"]["count"][k], r["state"]["min_fp"][k]) == (len(mine), mine[0] if mine else None), (r["level"], r["kind"], state_preds[k][0])
+        print("beyond the buffers %s: level %d %s, %d states, state hits %s" % (key, r["level"], r["kind"], len(lv), dict(zip((p[0] for p in state_preds), r["state"]["count"]))))
+        if probed:
+            assert r["step"] is None
+            continue
+        assert r["state"]["n_states"] == len(lv)
+        pairs = []
+        for fp, rec in lv.items():
+            pn = _norm(S.fixed, rec)
+            for s in succ_of[fp]:
+                bits = sr.bits_of(step_preds, _view(key, pn), _view(key, _norm(S.fixed, s["words"])), orc.ACTIONS[s["action"]])
+                pairs.append((fp, bits))
+        assert (r["step"]["n_states"], r["step"]["n_pairs"], r["step"]["n_err"]) == (len(lv), len(pairs), 0), r["level"]
+        hitp = sorted(x for x in pairs if x[1])
+        assert sorted(tuple(x) for x in r["pairs"]) == hitp and r["n_hit_pairs"] == len(hitp), r["level"]
+        for k in range(len(step_preds)):
+            mine = [fp for fp, b in hitp if (b >> k) & 1]
+            assert (r["step"]["count"][k], r["step"]["min_fp"][k]) == (len(mine), mine[0] if mine else None), (r["level"], step_preds[k][0])
+        print("beyond the buffers %s: level %d, %d pairs, step hits %s" % (key, r["level"], len(pairs), dict(zip((p[0] for p in step_preds), r["step"]["count"]))))
+    assert sorted(seen) == [(2, False), (3, False), (4, True)], sorted(seen)
+    assert sum(seen[(4, True)]["state"]["count"]) > 0 and sum(seen[(3, False)]["step"]["count"]) > 0

@@ -93,15 +93,18 @@ def _assert_report_equals_model(r, want, state_preds, step_preds, n_walkers):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. exact counts against the model
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R, C, n, L, max_depth", [(3, 1, 2, 1, 12), (2, 1, 1, 1, 30), (5, 1, 2, 1, 40), (4, 1, 2, 1, 40)])
+@pytest.mark.parametrize("R, C, n, L, max_depth", [(3, 1, 2, 1, 12), (2, 1, 1, 1, 30), (5, 1, 2, 1, 40), (4, 1, 2, 1, 40), (3, 2, 3, 1, 40)])
 def test_report_counts_equal_the_model(vt, R, C, n, L, max_depth):
     """100 walkers: the second wave has 36 walkers and 28 idle lanes, which must count nothing.  (2,1,1,1) has 76 states and its walks end in terminal
     states at different times: lanes of one wave start and step in the same iteration.  At five and four replicas (replica blocks of four words, broadcasts
     that append R - 1 bag entries to the walker's record in place) the walks run 40 steps deep, far enough to hold DoViewChanges, and a second pair of
-    programs — the R >= 4 sets of deep_predicates_reference.py — is counted over the same walks."""
+    programs — the R >= 4 sets of deep_predicates_reference.py — is counted over the same walks.  (3,2,3,1), under the policy assume_commit_number: two clients,
+    and the second pair of programs is the two-client sets — both rows of the client tables, client_id = 2 in logs and messages, the row ReceivePrepareMsg
+    rewrites for the other client — over walks of 40 steps."""
     from oracle import pycodec, pyoracle as po
-    m = vt.Model.from_constants(R=R, C_=C, n=n, L=L)
-    PM = po.Model(R, C, tuple("v%d" % (i + 1) for i in range(n)), L)
+    policy = dict(assume_commit_number=True) if C == 2 else {}
+    m = vt.Model.from_constants(R=R, C_=C, n=n, L=L, **policy)
+    PM = po.Model(R, C, tuple("v%d" % (i + 1) for i in range(n)), L, **policy)
     ws, wp = m.compile_predicates(wr.text_of(wr.SET_A)), m.compile_step_predicates(sr.text_of(sr.SET_A))
     want = _model_counts(vt, m, lambda words: pycodec.unpack(PM, words), wr.SET_A, wr.bits_of, sr.SET_A, sr.bits_of, 100, max_depth, 11, 64)
     r = m.simulate_where(state=ws, step=wp, stop=False, n_walkers=100, max_depth=max_depth, seed=11, max_rounds=1)
@@ -125,6 +128,19 @@ def test_report_counts_equal_the_model(vt, R, C, n, L, max_depth):
         print("simulate_where (%d,%d,%d,%d): n_walkers 100, max_depth %d, seed 11, max_rounds 1; the model stands on %d states in which a DoViewChange is held "
               "and takes %d pairs on which the held set grew" % (R, C, n, L, max_depth, held, grew))
         assert held >= 1 and grew >= 1                                 # by the Python model, which does not run the kernel under test
+    if C == 2:
+        ws2, wp2 = m.compile_predicates(dp.text_of(dp.STATE_C2)), m.compile_step_predicates(dp.text_of(dp.STEP_C2))
+        want2 = _model_counts(vt, m, lambda words: pycodec.unpack(PM, words), dp.STATE_C2, wr.bits_of, dp.STEP_C2, sr.bits_of, 100, max_depth, 11, 64)
+        r2c = m.simulate_where(state=ws2, step=wp2, stop=False, n_walkers=100, max_depth=max_depth, seed=11, max_rounds=1)
+        _assert_report_equals_model(r2c, want2, dp.STATE_C2, dp.STEP_C2, 100)
+        assert (want2["steps"], want2["walks"]) == (want["steps"], want["walks"]) and want["walks"] > 100
+        pending = want2["cs"][[p[0] for p in dp.STATE_C2].index(dp.SIM_C2_STATE_MUST_HIT)]
+        appended = want2["cp"][[p[0] for p in dp.STEP_C2].index(dp.SIM_C2_STEP_MUST_HIT)]
+        print("simulate_where (%d,%d,%d,%d): the model stands on %d states in which a request of client 2 is pending and takes %d pairs that append an entry of "
+              "client 2" % (R, C, n, L, pending, appended))
+        rewritten = [want2["cp"][[p[0] for p in dp.STEP_C2].index(nm)] for nm in ("Row2RewrittenByClient1", "Row1RewrittenByClient2")]
+        print("... and %d + %d pairs on which ReceivePrepareMsg rewrites the row of the client whose entry it did not append" % tuple(rewritten))
+        assert pending >= 1 and appended >= 1 and min(rewritten) >= 1  # by the Python model, which does not run the kernel under test
 
 
 # ---------------------------------------------------------------------------------------------------------------------

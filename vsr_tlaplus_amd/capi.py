@@ -226,6 +226,7 @@ SYMBOLS = {
 # test hooks: exported by libvsrmc_hooks.so only (-DVSRMC_TEST_HOOKS; VSRMC_LIB points a test's child process at it), declared when present
 HOOK_SYMBOLS = {
     "vsrmc_test_checker_seed_records": (C.c_int32, [V, V, V, C.c_uint64]),
+    "vsrmc_test_checker_extra_launches": (C.c_int32, [V, C.POINTER(C.c_uint64)]),
     # csrc/host_test_table.hpp: the seen-set kernels of a checker, k_partition and a stand-alone winner set, one launch at a time (tests/seen_set_worker.py)
     "vsrmc_test_table_clear": (C.c_int32, [V]),
     "vsrmc_test_table_claim": (C.c_int32, [V, V, C.c_uint64, C.c_int32, C.c_int32, V, V]),

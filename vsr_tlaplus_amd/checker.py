@@ -498,6 +498,16 @@ class ModelChecker:
         self.n_frontier = self.distinct = len(off) - 1
         self.levels = [dict(level=1, n_new=len(off) - 1, generated=0, deadlocks=0, seeded=True)]
 
+    def extra_launches(self):
+        """TEST HOOK (the hooks library only): the checker's running count of k_expand launches beyond a pass's first one — a stored step adds one per
+        list of overflowed tiles it launches again."""
+        fn = getattr(capi.load(), "vsrmc_test_checker_extra_launches", None)
+        if fn is None:
+            raise RuntimeError("vsrmc_test_checker_extra_launches is a test hook: load libvsrmc_hooks.so (VSRMC_LIB)")
+        n = C.c_uint64()
+        check(fn(self._h, C.byref(n)))
+        return n.value
+
     def step(self):
         info = capi.LevelInfo()
         check(capi.load().vsrmc_checker_step(self._h, C.byref(info)))

@@ -175,7 +175,11 @@ KernelSet kernels_for(const Model& M) {
     case 311: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 311>, false};
     case 312: return full_set<312>(k_expand<true, 312, EXPAND_PLAIN5>);   // BASELINE configs[1]: its ordinary level fits 96 registers (two permutations)
     case 313: return full_set<313>();
-    case 323: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 323>, false};
+    case 323: {                                                  // BASELINE configs[3] (two clients): the ordinary level has its own instantiation, which writes a tile
+      KernelSet k{k_expand<false, 0>, k_materialize<0>, k_expand<true, 323>, false};   // that overflows the work list down to be taken again in halves (REDO_OK)
+      k.plain = k_expand<true, 323, EXPAND_PLAIN>;
+      return k;
+    }
     case 412: return {k_expand<false, 0>, k_materialize<0>, k_expand<true, 412>, false};
     case 512: return full_set<512>();
     case 1302: {                                                 // the shipped VR_STATE_TRANSFER.cfg

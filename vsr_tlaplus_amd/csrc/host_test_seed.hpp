@@ -104,5 +104,13 @@ int32_t vsrmc_test_checker_seed_records(vsrmc_checker* c, const uint64_t* words,
   return 0;
 }
 
+// How often a list of overflowed tiles was launched again (redo_overflowed_tiles) and the other k_expand launches beyond a pass's first one: the
+// checker's running counter.  A stored step adds to it and never resets it: a test reads it before and after the step.
+int32_t vsrmc_test_checker_extra_launches(vsrmc_checker* c, uint64_t* out) {
+  if (!c || !out) return fail(VSRMC_E_ARG, "null argument");
+  *out = c->extra_launches;
+  return 0;
+}
+
 }  // extern "C"
 #endif
