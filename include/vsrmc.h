@@ -334,6 +334,56 @@ int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_wher
 int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_where_info* out);
 int32_t vsrmc_checker_where_states(vsrmc_checker* c, uint64_t* fps, uint8_t* bits, uint64_t cap, uint64_t* n);
 
+/* ---- state constraints: where the search does not go (TLC's CONSTRAINT) ---------------------------------------------
+ * One exported predicate of a state program (vsrmc_predicates_compile / vsrmc_where_compile) attached to a checker.  A successor that fails it is OUT OF
+ * MODEL: it is generated and counted in `generated`, the built-in invariants are checked on it, but it is no distinct state, is not expanded and is never
+ * a parent in a trace; an in-model state that is reachable only through out-of-model states is NOT reached.  Init is subject to it.  Deadlock stays "no
+ * successor generated", in the model or not.  [TLC-RECALLED: these semantics are written from memory of tlc2.tool.Worker / ModelChecker.doNext; they
+ * are not pinned against a TLC run.]  A CONSTRAINT section of a cfg stays refused at load: the constraint is attached through this interface only.
+ * How: k_constrain (csrc/vsr_constrain.hpp) runs over every level vsrmc_checker_step has just committed, before the call returns, and withdraws the
+ *   states that fail (their index slots become unused ones); they keep their seen-set slot.  In the vsrmc_level_info of such a step n_new, distinct and
+ *   record_words are the in-model figures; generated, act_generated and viol_* stay k_expand's.  A built-in violation on an out-of-model state is
+ *   reported as ever, with viol_index ~0: its behaviour is vsrmc_checker_trace_fp(c, level, viol_fp, ...).  A level of which nothing is in the model ends
+ *   the search like a level without new states (n_new 0, the checker stays at the level before; the pruned level can still be traced by fingerprint).
+ *   Terminal, where and step scans of a stored level see the in-model states; pruned_count / pruned_min_fp_k below are the same program's other exported
+ *   predicates over the PRUNED states, so that a user's invariant is not lost on them.
+ * vsrmc_checker_constrain_attach: accepted only on a checker at level 1 (fresh, or after vsrmc_checker_reset); evaluates Init at once — Init out of
+ *   model: the level is empty, distinct 0, the next step reports an exhausted search.  vsrmc_checker_reset keeps the attachment and evaluates Init again.
+ *   w == NULL detaches and starts the search over.  The program is copied; its device buffers are allocated once per attachment.
+ *   Refused: VSRMC_E_ARG for a step program, a program compiled for another model, a name_index the program does not export, and a program that reads
+ *   aux_svc or aux_client_acked (outside VIEW: the copy of a state that arrived first would decide its membership; under SYMMETRY the compiler already
+ *   refuses value literals, so every accepted predicate is symmetric); VSRMC_E_STATE on a sharded checker (world > 1), after level 1, with predicates
+ *   attached by vsrmc_checker_deep_attach, and for a second attachment.
+ * While a constraint is attached: vsrmc_checker_deepen, _probe, _probe2, _probe3, _deep_attach and _save are refused (VSRMC_E_STATE: the levels beyond
+ *   the record buffers are not constrained; a checkpoint does not name the constraint).  vsrmc_checker_advance stores levels only: when the next level is
+ *   not predicted to fit, or overflowed, it returns 0 with *what = 4 and the reason in vsrmc_last_error(); vsrmc_check then stops with stop_reason 5.
+ *   The seen-set: a pruned state is no distinct state but keeps its slot, so vsrmc_checker_room counts distinct PLUS every state pruned since the search started
+ *   as the table's load (it grows the table, or reports it full, by that figure).  The record buffers: k_expand writes a level before the filter runs, so the
+ *   prediction of vsrmc_checker_advance scales the in-model figures by (kept + pruned) / kept of the newest filtered level; a level that overflows all the same is
+ *   the *what = 4 stop in the single-pass scheme.  Under exact_ties there is neither prediction nor that path: an overflow is the plain "frontier full" error
+ *   (VSRMC_E_REP) and the checker has failed.
+ * vsrmc_checker_constraint_info: the figures of one filtered level (level 1 = Init; level 0 asks for the newest filtered one).  kept_xor / kept_sum / kept are what vsrmc_checker_level_checksum
+ *   gives for the filtered level, without a second pass.
+ * vsrmc_checker_constraint_pruned: the fingerprints of the newest filtered level's pruned states, ascending; fps == NULL asks for the number.  The
+ *   contract of vsrmc_checker_where_states: at most 2^20 are kept (the same test knob VSRMC_WHERE_LIST_CAP=N lowers that), beyond that *n is the true
+ *   number and the call returns VSRMC_E_REP; counts and minima are exact regardless.  The list is copied from the device and sorted by the first call after a level
+ *   was filtered, not by the step: a run that never asks pays nothing for it.
+ * (Test knob: the environment variable VSRMC_CONSTRAIN_GRID=N caps k_constrain's grid at N blocks, so that a small level drives its grid-stride loop
+ *   through several trips; it has no other use.) */
+typedef struct vsrmc_constraint_info {
+  int32_t level, k;                                /* the level filtered; the exported predicate that is the constraint */
+  uint64_t n_states;                               /* states of the level as k_expand left it = kept + pruned */
+  uint64_t kept, pruned;
+  uint64_t kept_xor, kept_sum;                     /* xor / sum mod 2^64 of the in-model fingerprints */
+  uint64_t kept_max_bag, kept_words;               /* largest bag and record words among the in-model states */
+  uint64_t pruned_min_fp;                          /* the smallest pruned fingerprint; ~0 if none */
+  uint64_t pruned_count[8], pruned_min_fp_k[8];    /* per exported predicate p: PRUNED states with bit p set, the smallest fingerprint among them (~0 if none) */
+  double kernel_ms;                                /* HIP-event time of k_constrain */
+} vsrmc_constraint_info;
+int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, int32_t name_index);
+int32_t vsrmc_checker_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_constraint_info* out);
+int32_t vsrmc_checker_constraint_pruned(vsrmc_checker* c, uint64_t* fps, uint64_t cap, uint64_t* n);
+
 /* ---- step predicates: user-written predicates over a state AND its successor, checked on every transition -------------------------
  * The safety half of PROPERTY: an action property [][P]_vars is a predicate over a (state, successor) pair.  The language of the state predicates
  * plus primed variables (rep_view_number'[r], Len(rep_log[r])', (...)', \A m \in DOMAIN messages', messages'[m]), UNCHANGED e and step_action (the
@@ -541,7 +591,8 @@ int32_t vsrmc_checker_load(const vsrmc_model* m, const vsrmc_options* o, const c
 
 /* ≙ tlc2.tool.ModelChecker.runTLC / Worker.run until the queue is empty, an invariant fails, a bound is hit or the spec raises an
  * evaluation error: vsrmc_checker_step in a loop.  stop_reason: 0 exhausted, 1 invariant violated (last->viol_*), 2 max_depth,
- * 3 max_seconds; errors come back as the return code, with `last` describing the last completed level. */
+ * 3 max_seconds, 4 the seen-set is full, 5 a constraint is attached and the next level does not fit the record buffers (the levels beyond them are
+ * not constrained: the search is incomplete at last->level; the reason is in vsrmc_last_error()); errors come back as the return code, with `last` describing the last completed level. */
 int32_t vsrmc_check(vsrmc_checker* c, int32_t max_depth, double max_seconds, int32_t* stop_reason, vsrmc_level_info* last);
 
 /* ---- StateQueue ≙ tlc2.tool.queue.StateQueue (sEnqueue(TLCState[]) / sDequeue(int) / size): a FIFO of state records kept in

@@ -56,6 +56,12 @@ class WhereInfo(C.Structure):
                 ("min_index", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
 
 
+class ConstraintInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("k", C.c_int32), ("n_states", C.c_uint64), ("kept", C.c_uint64), ("pruned", C.c_uint64), ("kept_xor", C.c_uint64),
+                ("kept_sum", C.c_uint64), ("kept_max_bag", C.c_uint64), ("kept_words", C.c_uint64), ("pruned_min_fp", C.c_uint64),
+                ("pruned_count", C.c_uint64 * 8), ("pruned_min_fp_k", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
+
+
 class StepInfo(C.Structure):
     _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("n_pairs", C.c_uint64), ("n_err", C.c_uint64),
                 ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8), ("min_index", C.c_uint64 * 8), ("min_ordinal", C.c_uint32 * 8),
@@ -153,6 +159,9 @@ SYMBOLS = {
     "vsrmc_where_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V]),
     "vsrmc_checker_where_scan": (C.c_int32, [V, V, C.POINTER(WhereInfo)]),
     "vsrmc_checker_where_states": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
+    "vsrmc_checker_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ConstraintInfo)]),
+    "vsrmc_checker_constraint_pruned": (C.c_int32, [V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_step_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_predicates_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64)]),

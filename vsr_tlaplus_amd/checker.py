@@ -436,6 +436,9 @@ class ModelChecker:
         self.model = model
         self._deep = None                                            # (state Where, step Where) of deep_attach, or None
         self._deep_seen = set()                                      # (level, probed) pairs run(deep=True) has looked at
+        self._constraint = None                                      # (Where, k) of constrain(), or None
+        self.stopped = None                                          # the reason advance() gave for ("stopped", ..)
+        self._pruned_checked = 0                                     # the newest filtered level run(never=..) has looked at
         o = capi.Options()
         capi.load().vsrmc_options_default(C.byref(o))
         o.device, o.table_log2 = device, table_log2
@@ -478,11 +481,83 @@ class ModelChecker:
         self.rebased = []
         self.deadlock = None
         self.witness = None
+        self.stopped = None
+        self._pruned_checked = 0
 
     def reset(self):
-        """Back to Init with an empty seen-set; keeps the HBM allocations (a fresh TLC run on the same model)."""
+        """Back to Init with an empty seen-set; keeps the HBM allocations (a fresh TLC run on the same model).  A constraint stays attached: Init is
+        evaluated again."""
         check(capi.load().vsrmc_checker_reset(self._h))
         self._fresh()
+        self._after_init_filter()
+
+    def _after_init_filter(self):
+        if self._constraint is not None:
+            st = capi.LevelInfo()
+            check(capi.load().vsrmc_checker_status(self._h, C.byref(st)))
+            self.n_frontier, self.distinct = st.n_new, st.distinct
+            self.levels = [dict(level=1, n_new=st.n_new, generated=0, deadlocks=0)]
+
+    def constrain(self, where, name=None):
+        """Attach a state constraint (TLC's CONSTRAINT; vsrmc_checker_constrain_attach): the exported predicate `name` (a name or a number; None: the
+        program's only one) of the state program `where` (Model.compile_predicates).  A state that fails it is out of model: counted in `generated`,
+        checked against the built-in invariants, but no distinct state, never expanded, never a parent in a trace.  At level 1 only (a fresh checker, or
+        after reset()); Init is evaluated at once.  where=None detaches and starts over.  While attached, levels are stored only: advance() returns
+        ("stopped", ..) and run() "constraint-out-of-room" when the next level does not fit the record buffers; deepen / probe / deep_attach / save
+        are refused."""
+        if where is None:
+            check(capi.load().vsrmc_checker_constrain_attach(self._h, None, 0))
+            self._constraint = None
+            self._fresh()
+            return
+        if name is None:
+            if len(where.names) != 1:
+                raise ValueError("the program exports %d predicates: name the constraint" % len(where.names))
+            name = 0
+        k = name if isinstance(name, int) else where.names.index(name)
+        check(capi.load().vsrmc_checker_constrain_attach(self._h, where._h, k))
+        self._constraint = (where, k)
+        self._fresh()
+        self._after_init_filter()
+
+    def constraint_results(self, level=None):
+        """The figures of the filtered levels (vsrmc_checker_constraint_info) -> [dict(level, k, n_states, kept, pruned, kept_xor, kept_sum, kept_max_bag,
+        kept_words, pruned_min_fp, pruned_count={name: n}, pruned_min_fp_k={name: fp or None}, kernel_ms)], level 1 (Init) first; level=L: that
+        level's dict.  pruned_count / pruned_min_fp_k: the program's exported predicates over the PRUNED states of the level."""
+        if self._constraint is None:
+            raise ValueError("no constraint attached (constrain)")
+        w = self._constraint[0]
+        none = (1 << 64) - 1
+
+        def one(lv):
+            ci = capi.ConstraintInfo()
+            check(capi.load().vsrmc_checker_constraint_info(self._h, lv, C.byref(ci)))
+            d = {n: getattr(ci, n) for n, _ in ci._fields_ if n not in ("pruned_count", "pruned_min_fp_k")}
+            d["pruned_min_fp"] = None if ci.pruned_min_fp == none else int(ci.pruned_min_fp)
+            d["pruned_count"] = {nm: int(ci.pruned_count[p]) for p, nm in enumerate(w.names)}
+            d["pruned_min_fp_k"] = {nm: (None if ci.pruned_min_fp_k[p] == none else int(ci.pruned_min_fp_k[p])) for p, nm in enumerate(w.names)}
+            return d
+        if level is not None:
+            return one(level)
+        out, lv = [], 1
+        while True:
+            try:
+                out.append(one(lv))
+            except VsrmcError:
+                return out
+            lv += 1
+
+    def constraint_pruned(self):
+        """The pruned states of the newest filtered level -> fingerprints ascending (vsrmc_checker_constraint_pruned).  More than the list holds:
+        VsrmcError (-5) that names the true number; the counts and minima of constraint_results() are exact regardless."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_constraint_pruned(self._h, None, 0, C.byref(n))
+        if rc not in (0, -5):
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        check(lib.vsrmc_checker_constraint_pruned(self._h, _p(fps), len(fps), C.byref(n)))
+        return fps[: n.value].copy()
 
     def seed_records(self, words, off):
         """TEST HOOK (the hooks library only: csrc/host_test_seed.hpp): start the search from the wire records words[off[i] : off[i + 1]] instead of
@@ -517,12 +592,20 @@ class ModelChecker:
         if d["n_new"]:
             self.levels.append(d)
         if d["viol_mask"] and self.violation is None:
-            self.violation = dict(level=d["level"], index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"])
+            self.violation = dict(level=self._viol_level(d), index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"])
         return d
+
+    def _viol_level(self, d):
+        """the level of the violator a step reported.  With a constraint attached it is the newest FILTERED level: when every state of that level is out of
+        model the checker steps back to the level before (d["level"]), the violator is a state of the level after it"""
+        if self._constraint is None:
+            return d["level"]
+        return self.constraint_results(0)["level"]
 
     def check(self, max_depth=0, max_seconds=0.0):
         """≙ ModelChecker.runTLC in one native call (vsrmc_check: the automatic level scheme)
-        -> "exhausted" | "violation" | "max-depth" | "max-seconds" | "seen-set-full"."""
+        -> "exhausted" | "violation" | "max-depth" | "max-seconds" | "seen-set-full" | "constraint-out-of-room" (a constraint is attached and the
+        next level does not fit the record buffers: self.stopped = the reason)."""
         reason = C.c_int32()
         info = capi.LevelInfo()
         check(capi.load().vsrmc_check(self._h, max_depth, max_seconds, C.byref(reason), C.byref(info)))
@@ -534,9 +617,11 @@ class ModelChecker:
         self.level, self.n_frontier = st.level, st.n_new
         check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))   # (the seen-set may have grown)
         if reason.value == 1:
-            self.violation = dict(level=d["level"], index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"],
+            self.violation = dict(level=self._viol_level(d), index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"],
                                   probed=d["viol_index"] == (1 << 64) - 1)
-        return ["exhausted", "violation", "max-depth", "max-seconds", "seen-set-full"][reason.value]
+        if reason.value == 5:
+            self.stopped = capi.load().vsrmc_last_error().decode()
+        return ["exhausted", "violation", "max-depth", "max-seconds", "seen-set-full", "constraint-out-of-room"][reason.value]
 
     def _deep_dict(self, info):
         d = info.as_dict()
@@ -565,6 +650,9 @@ class ModelChecker:
             self.level, self.n_frontier = a.level, a.n_new
             self.rebased.append(dict(level=a.level, n=a.n_new, seconds=a.seconds, launches=a.pending))
             check(capi.load().vsrmc_checker_advance(self._h, C.byref(a), C.byref(b), C.byref(what)))
+        if what.value == 4:                          # a constraint is attached and the next level does not fit: nothing was done
+            self.stopped = capi.load().vsrmc_last_error().decode()
+            return "stopped", a.as_dict(), None
         if what.value == 1:
             d = a.as_dict()
             self.level, self.n_frontier, self.distinct = d["level"], d["n_new"], d["distinct"]
@@ -572,7 +660,7 @@ class ModelChecker:
             if d["n_new"]:
                 self.levels.append(d)
             if d["viol_mask"] and self.violation is None:
-                self.violation = dict(level=d["level"], index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"])
+                self.violation = dict(level=self._viol_level(d), index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"])
             return "level", d, None
         da, db = self._deep_dict(a), self._deep_dict(b)
         self.depth, self.distinct = da["level"], da["distinct"]
@@ -593,6 +681,10 @@ class ModelChecker:
         stored while they fit the record buffers, the search goes on beyond them through the seen-set alone (deepen).
         check_deadlock (TLC's default, off here): every stored level is scanned for terminal states before it is expanded; the first level
         that has one ends the run with "deadlock" — self.deadlock = the scan's result, deadlock_trace() the behaviour.
+        With a constraint attached (constrain) the scans see the in-model states, and `never` is checked on the states each level prunes as well (Init
+        included) — through the figures k_constrain keeps for every predicate its own program exports: that program must export every name of `never`
+        (ValueError otherwise; that the two definitions of a name agree is the caller's business: compile both from one text).  self.witness then has
+        pruned=True and index None.
         reach / never (a Where each, off by default): every stored level is scanned (k_where) before it is expanded, where check_deadlock scans.  The
         first level with a state that satisfies a predicate of `reach` ends the run with "reached"; one that satisfies a predicate of `never` (the
         negation of a user's invariant) ends it with "violation".  self.witness = dict(level, k, name, fp, index, kind); witness_trace() the behaviour.
@@ -606,6 +698,11 @@ class ModelChecker:
         ("regenerated", "inserted", "probed") and index None (a step hit: no ordinal either); deep_witness_trace() is the behaviour."""
         import time
         t0 = time.time()
+        if never is not None and self._constraint is not None:
+            missing = [nm for nm in never.names if nm not in self._constraint[0].names]
+            if missing:
+                raise ValueError("run(never=..) with a constraint attached: the constraint's program does not export %s, so the states it prunes would not be "
+                                 "checked against them — define the predicates of `never` in the text the constraint was compiled from as well" % ", ".join(missing))
         deep_state = deep_step = None
         if deep:
             if never is not None and reach is not None:
@@ -649,7 +746,13 @@ class ModelChecker:
                         self.witness = dict(level=t["level"], k=k, name=w.names[k], fp=t["min_fp"][k], index=t["min_index"][k], kind=kind,
                                             ordinal=t["min_ordinal"][k], action=ACTION_NAMES[t["min_action"][k]])
                         return kind
+            if never is not None and self._never_on_pruned(never):          # (Init, when it is out of model)
+                return "violation"
             kind, d, p = self.advance()
+            if kind == "stopped":
+                return "constraint-out-of-room"
+            if never is not None and self._never_on_pruned(never):
+                return "violation"
             if deep and kind == "deep":
                 hit = self._deep_first_hit(deep_state, deep_step, stop_on_violation)
                 if hit is not None:
@@ -658,6 +761,22 @@ class ModelChecker:
                 return "exhausted"
             if self.violation is not None and stop_on_violation:
                 return "violation"
+
+    def _never_on_pruned(self, never):
+        """run(never=..) with a constraint attached: the user's invariant on the states the newest filtered level pruned, if that level has not been looked at
+        yet (TLC checks an invariant before the constraint).  k_constrain evaluates its WHOLE program on every pruned state, so the figures exist for the
+        predicates the constraint's program exports: run() has checked that it exports every name of `never`.  -> True: self.witness is set"""
+        if self._constraint is None:
+            return False
+        r = self.constraint_results(0)
+        if r["level"] <= self._pruned_checked:
+            return False
+        self._pruned_checked = r["level"]
+        hits = [nm for nm in never.names if r["pruned_count"][nm]]
+        if not hits:
+            return False
+        self.witness = dict(level=r["level"], k=never.names.index(hits[0]), name=hits[0], fp=r["pruned_min_fp_k"][hits[0]], index=None, kind="violation", pruned=True)
+        return True
 
     def _deep_first_hit(self, deep_state, deep_step, stop_on_violation):
         """the results of the levels the last advance() examined for the first time -> the run's verdict, or None"""
@@ -687,6 +806,8 @@ class ModelChecker:
     def violation_trace(self):
         """the counter-example of the violation run() / advance() reported, wherever it was found"""
         v = self.violation
+        if self._constraint is not None:             # (the violator may be out of model: its index slot is withdrawn, its seen-set slot is not)
+            return self.trace_fp(v["level"], v["fp"])
         return self.probe_trace() if v.get("probed") else self.trace(v["level"], v["index"])
 
     def terminal_scan(self):

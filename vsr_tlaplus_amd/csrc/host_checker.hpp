@@ -15,6 +15,7 @@ struct PassDst {            // where a pass writes (records, refs, fingerprints)
 };
 struct DeepLevelRec { u64 n_new = 0, n_local = 0, generated = 0, max_bag = 0, frontier = 0; };   // n_local: this rank's share (unsharded: all)   // a level that exists in the seen-set only (vsr_deep.hpp)
 struct vsrmc_deep_attach;    // a user's predicates on the levels beyond the record buffers (host_deep_where.hpp)
+struct vsrmc_constraint;     // a user's state constraint, applied to every level right after it is committed (host_constrain.hpp)
 struct vsrmc_checker {
   vsrmc_model model;
   vsrmc_options opt;
@@ -123,6 +124,8 @@ struct vsrmc_checker {
   u64 step_total = 0;
   int step_level = -1;
   vsrmc_deep_attach* deep_attach = nullptr;   // vsrmc_checker_deep_attach (host_deep_where.hpp): programs, persistent device buffers, per-level results; not part of a checkpoint
+  u64 table_pruned = 0;                       // states the constraint pruned since the search started: no distinct states, but each keeps its seen-set slot (vsrmc_checker_room)
+  vsrmc_constraint* constraint = nullptr;     // vsrmc_checker_constrain_attach (host_constrain.hpp): the program, its device buffers, per-level results; a checkpoint is refused while attached
 #ifdef VSRMC_TEST_HOOKS
   // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
   std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending
@@ -141,6 +144,13 @@ void deep_attach_free(vsrmc_checker* c);
 int deep_where_begin(vsrmc_checker* c, int last_level);
 int deep_where_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, int kind, u64 bag, bool probe_next);
 int deep_where_end(vsrmc_checker* c, int rc);
+// host_constrain.hpp (defined there, as above): the filter step_local runs on the level it has just committed; a search that starts over keeps the
+// attachment and evaluates Init again; a checker that is destroyed frees it; 1 while the seen-set holds one level beyond c->level of which every state was pruned
+int constrain_level(vsrmc_checker* c, vsrmc_level_info* info);
+int constraint_restart(vsrmc_checker* c);
+void constraint_free(vsrmc_checker* c);
+int constraint_beyond(const vsrmc_checker* c);
+double constraint_write_ratio(const vsrmc_checker* c);   // states k_expand wrote per state the filter kept, in the newest filtered level (1 without a constraint)
 typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*, u64, u64*, u64, LevelCtl*, int, int, u64*, u64, u32, u64*,
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,
@@ -406,7 +416,8 @@ int checker_seed(vsrmc_checker* c) {
   c->probe_viol_key.clear();
   c->probe_viol_level = 0;
   deep_attach_restart(c);
-  return 0;
+  c->table_pruned = 0;
+  return constraint_restart(c);                                 // (no constraint attached: nothing)
 }
 }  // namespace
 
@@ -923,6 +934,7 @@ static int32_t step_local(vsrmc_checker* c, vsrmc_level_info* info) {
   }
   rc = phase_commit(c, info);
   if (rc) return rc;
+  if (c->constraint && (rc = constrain_level(c, info))) return rc;   // before anything else reads the level (a violator that is out of model: viol_index ~0, vsrmc_checker_trace_fp)
   if (info->viol_mask) return find_fp_newest(c, info->viol_fp, &info->viol_index);
   return 0;
 }

@@ -39,6 +39,7 @@ bool file_to_dev(FILE* f, void* d_ptr, u64 bytes, std::vector<char>& buf) {
 int32_t vsrmc_checker_save(vsrmc_checker* c, const char* path) {
   if (!c || !path) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->failed) return fail(VSRMC_E_STATE, "the checker stopped on an error");
+  if (c->constraint) return fail(VSRMC_E_STATE, "checkpoint: a constraint is attached (vsrmc_checker_constrain_attach); a checkpoint does not name it, and a recovery would go on unconstrained");
   if (c->opt.world > 1 && c->opt.exact_ties) return fail(VSRMC_E_STATE, "checkpoints of sharded exact-mode checkers are not supported");
   // (a sharded search beyond its record buffers: the rank's winner set travels in a section of its own behind the frontier, the level loop's own state —
   // the run's totals, the violation — in a sidecar the loop writes: vsrmc_shard_loop_save)
@@ -499,7 +500,7 @@ int32_t vsrmc_checker_trace_fp(vsrmc_checker* c, int32_t level, uint64_t fp, uin
                                int32_t* actions, uint64_t cap_states, uint64_t* n_states) {
   if (!c || !words || !off || !actions || !n_states) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "sharded checker: walk the predecessor pointers with vsrmc_checker_lookup on every rank");
-  if (level < 1 || level > c->level + c->deep) return fail(VSRMC_E_ARG, "no such level");   // (a seen-set-only level is walked like any other: the walk needs no records)
+  if (level < 1 || level > c->level + c->deep + constraint_beyond(c)) return fail(VSRMC_E_ARG, "no such level");   // (a seen-set-only level is walked like any other: the walk needs no records)
   HIPCHK(hipSetDevice(c->opt.device));
   std::vector<u64> fps;
   int rc = walk_trace(c, fp, level, &fps);                     // through the seen-set, back to Init, on the device
@@ -532,6 +533,7 @@ void vsrmc_checker_destroy(vsrmc_checker* c) {
   if (!c) return;
   (void)hipSetDevice(c->opt.device);
   deep_attach_free(c);
+  constraint_free(c);
   if (c->table) (void)hipFree(c->table);
   for (int b = 0; b < 2; b++) {
     if (c->words[b]) (void)(((c->host_frontier >> b) & 1) ? hipHostFree(c->words[b]) : hipFree(c->words[b]));

@@ -12,6 +12,7 @@ int32_t vsrmc_checker_probe(vsrmc_checker* c, vsrmc_level_info* info) {
   // sharded: the rank probes its part of the newest level against ITS part of the seen-set; the violating successors it could
   // not find there (vsrmc_checker_probe_candidates) still have to be shown to their owners (sharded.py: ShardedChecker.probe)
   if (c->opt.exact_ties) return fail(VSRMC_E_STATE, "probe levels need a single-pass checker");
+  if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->failed && c->failed_code != ERR_FRONTIER_FULL) return fail(VSRMC_E_STATE, "the checker stopped on an error");
   c->failed = 0;
   c->probe_fp = 0;
@@ -216,6 +217,7 @@ static bool next_level_fits(const vsrmc_checker* c) {
   double pred;
   if (n < 32768 || c->hist_new[0] == 0) pred = (double)n * (double)std::max<u64>(2, c->g_last) * 1.25;
   else pred = (double)n * std::min((double)c->g_last, (double)c->hist_new[1] / (double)c->hist_new[0] * 1.02);
+  pred *= constraint_write_ratio(c);                             // n_valid / hist_new are in-model figures; k_expand writes the states the filter then prunes, too
   const double wbar = (double)std::max<u64>(c->cur_rec_w, (u64)c->model.M.fixed * n) / (double)n + 1.0;
   const int nxt = c->cur ^ 1;
   const double blocks = 4.0 * c->num_cus;                        // every resident block leaves a partly used word and index chunk behind
@@ -344,7 +346,7 @@ int32_t vsrmc_checker_room(vsrmc_checker* c, int32_t* state) {
   if (!c || !state) return fail(VSRMC_E_ARG, "NULL argument");
   *state = 0;
   const double slots = (double)(c->tmask + 1);
-  const double have = (double)(c->deep ? c->deep_distinct : c->distinct);   // (a sharded checker: this rank's share of both)
+  const double have = (double)(c->deep ? c->deep_distinct : c->distinct) + (double)c->table_pruned;   // (a sharded checker: this rank's share of both; a pruned state is no distinct state but holds a slot)
   const bool over = have > 0.85 * slots;
   if (!over && have + predicted_new(c) <= 0.85 * slots) return 0;
   if (c->opt.world > 1) { *state = over ? 2 : 0; return 0; }    // ranks grow nothing on their own: the level loop stops the run together
@@ -368,6 +370,23 @@ int32_t vsrmc_checker_advance(vsrmc_checker* c, vsrmc_level_info* a, vsrmc_level
   std::memset(b, 0, sizeof(*b));
   b->viol_fp = b->viol_index = ~(u64)0;
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "sharded checker: vsrmc_shard_loop_advance");
+  if (c->constraint) {                                           // levels are stored, or the run ends: no deep pass runs over a half-filtered search
+    auto no_room = [&](const char* why) {
+      *what = 4;
+      std::memset(a, 0, sizeof(*a));
+      a->level = c->level; a->n_new = c->n_valid; a->distinct = c->distinct; a->total_generated = c->total_generated;
+      a->viol_fp = a->viol_index = ~(u64)0;
+      (void)fail(0, std::string(why) + " at level " + std::to_string(c->level) + " (" + std::to_string((unsigned long long)c->distinct) +
+                        " in-model states): a constraint is attached, and the levels beyond the record buffers are not constrained - the search ends here, incomplete");
+      return 0;
+    };
+    if (c->failed && c->full_recoverable) return no_room("the next level overflowed the record buffers");
+    if (!c->opt.exact_ties && !next_level_fits(c)) return no_room("the next level is not predicted to fit the record buffers");
+    *what = 1;
+    const int rc = vsrmc_checker_step(c, a);
+    if (rc && c->failed && c->full_recoverable) return no_room("the next level overflowed the record buffers");
+    return rc;
+  }
   if (c->failed && c->full_recoverable) {                       // a vsrmc_checker_step the caller made itself ran out of record buffer: go on from the seen-set
     *what = 2;
     return adopt_overflowed_level(c, a);
@@ -409,6 +428,7 @@ int32_t vsrmc_check(vsrmc_checker* c, int32_t max_depth, double max_seconds, int
     int32_t what = 0;
     rc = vsrmc_checker_advance(c, &a, &b, &what);
     if (rc) return rc;
+    if (what == 4) { last->level = a.level; last->n_new = a.n_new; last->distinct = a.distinct; *stop_reason = 5; return 0; }   // a constraint is attached and the next level does not fit
     if (what == 3) continue;                                     // re-based: no new level, the next unit of progress is an ordinary level again
     *last = a;
     if (a.viol_mask) { *stop_reason = 1; return 0; }

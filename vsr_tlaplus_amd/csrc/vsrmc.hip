@@ -24,6 +24,7 @@
 #include "vsr_probe_scan.hpp"
 #include "vsr_terminal.hpp"
 #include "vsr_where.hpp"
+#include "vsr_constrain.hpp"
 #include "vsr_where_parse.hpp"
 #include "vsr_step.hpp"
 #include "vsr_deep_where.hpp"
@@ -121,6 +122,7 @@ extern "C" {
 #include "host_tlcfp.hpp"        // TLC's FP64 as a mode
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
+#include "host_constrain.hpp"    // state constraints: k_constrain over every level right after it is committed, per-level figures, the pruned list
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
 #include "host_deep_where.hpp"   // state / step predicates on the levels beyond the record buffers: attachment, per-level results, witnesses; k_probe_where
 #include "host_sim_where.hpp"    // simulation with state / step predicates on every walk: k_simulate_where

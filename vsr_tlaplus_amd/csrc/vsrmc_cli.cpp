@@ -97,6 +97,11 @@ static void usage() {
       "                    collision that hid a state under one function would have to repeat under the other (exit 13 if they differ)\n"
       "  -recover FILE     continue the search a checkpoint stopped at (same constants; buffer sizes may differ)\n"
       "  -noTLA            do not read / hash-check the .tla file (only the cfg)\n"
+      "  -constraint NAME  with -predicates FILE: the exported predicate NAME is a state constraint (TLC's CONSTRAINT): a state that fails it is generated,\n"
+      "                    counted and checked against the invariants, but it is no distinct state and is not explored further; Init is subject to it.  Levels\n"
+      "                    are stored only: when the next one does not fit the record buffers the run ends, incomplete (exit 4).  -invariant NAMES are checked\n"
+      "                    on the states the constraint prunes as well.  Not with -gpus N > 1, -simulate, -deepPredicates, -probeLast, -probe2At, -probe3At,\n"
+      "                    -checkpoint, -recover, -audit.  With -json the level lines carry \"kept\" and \"pruned\"\n"
       "  -json             one JSON object per level on stdout instead of TLC-style progress lines\n");
 }
 
@@ -147,15 +152,18 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
-  bool deep_predicates = false;
-  for (int i = 1; i < argc; i++)
+  bool deep_predicates = false, constrained = false;
+  for (int i = 1; i < argc; i++) {
     if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
+    if (std::string(argv[i]) == "-constraint") constrained = true;
+  }
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) {
       if (deep_predicates) { std::fprintf(stderr, "Error: -deepPredicates runs on one GPU: sharded checkers are not scanned (-gpus 1)\n"); return 2; }
+      if (constrained) { std::fprintf(stderr, "Error: -constraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
       return exec_sharded(argc, argv, i);
     }
-  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, steps_file, step_reach_arg, step_invariant_arg;
+  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, constraint_arg, steps_file, step_reach_arg, step_invariant_arg;
   bool where_report = false, step_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
@@ -206,6 +214,7 @@ int main(int argc, char** argv) {
     else if (a == "-reach" && i + 1 < argc) reach_arg = argv[++i];
     else if (a == "-invariant" && i + 1 < argc) invariant_arg = argv[++i];
     else if (a == "-whereReport") where_report = true;
+    else if (a == "-constraint" && i + 1 < argc) constraint_arg = argv[++i];
     else if (a == "-steps" && i + 1 < argc) steps_file = argv[++i];
     else if (a == "-stepReach" && i + 1 < argc) step_reach_arg = argv[++i];
     else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
@@ -216,6 +225,16 @@ int main(int argc, char** argv) {
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
   }
   if (cfg.empty()) { usage(); return 2; }
+  if (constrained) {                                              // refused before any device call
+    const char* why = constraint_arg.empty() ? "-constraint needs a NAME"
+                      : predicates_file.empty() ? "-constraint NAME needs -predicates FILE"
+                      : simulate ? "-constraint belongs to the exhaustive search: a random walk (-simulate) is not constrained"
+                      : deep_predicates ? "-constraint cannot be combined with -deepPredicates: the levels beyond the record buffers are not constrained"
+                      : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-constraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
+                      : (!chk_file.empty() || !recover_file.empty()) ? "-constraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
+                      : audit ? "-constraint cannot be combined with -audit" : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
   if (deep_predicates) {                                          // refused before any device call
     const bool state_query = !reach_arg.empty() || !invariant_arg.empty(), step_query = !step_reach_arg.empty() || !step_invariant_arg.empty();
     if (!state_query && !where_report && !step_query && !step_report) {
@@ -280,7 +299,9 @@ int main(int argc, char** argv) {
   }
   // state predicates (-predicates FILE): `w_all` = the file as written (-whereReport counts its exported names); `w_query` = the names of -reach, then
   // the negations of the names of -invariant, over the file with every definition made LOCAL
-  vsrmc_where *w_all = nullptr, *w_query = nullptr;
+  vsrmc_where *w_all = nullptr, *w_query = nullptr, *w_con = nullptr;   // w_con (-constraint): the negations of the names of -invariant, then the constraint
+  int con_index = -1;
+  std::vector<std::string> con_inv_names;
   std::vector<std::string> where_names, query_names;
   size_t n_reach = 0;
   auto split_names = [](const std::string& arg, std::vector<std::string>& out) {
@@ -334,7 +355,7 @@ int main(int argc, char** argv) {
       if (vsrmc_step_predicates_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
   }
-  if (!reach_arg.empty() || !invariant_arg.empty() || where_report) {
+  if (!reach_arg.empty() || !invariant_arg.empty() || where_report || constrained) {
     if (predicates_file.empty()) { std::fprintf(stderr, "Error: -reach / -invariant / -whereReport need -predicates FILE\n"); return 2; }
     std::ifstream pf(predicates_file, std::ios::binary);
     if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", predicates_file.c_str()); return 1; }
@@ -357,6 +378,18 @@ int main(int argc, char** argv) {
         local += "\nQuery" + std::to_string(k) + " == " + (k < n_reach ? "" : "~") + query_names[k];
       }
       if (vsrmc_predicates_compile(m, local.c_str(), &w_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+    }
+    if (constrained) {
+      bool known = false;
+      for (const std::string& n : where_names) known = known || n == constraint_arg;
+      if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", predicates_file.c_str(), constraint_arg.c_str()); return 2; }
+      split_names(invariant_arg, con_inv_names);
+      if (con_inv_names.size() > 7) { std::fprintf(stderr, "Error: -constraint with more than 7 -invariant names\n"); return 2; }
+      std::string local = make_local(text);
+      for (size_t k = 0; k < con_inv_names.size(); k++) local += "\nPrunedQuery" + std::to_string(k) + " == ~" + con_inv_names[k];
+      local += "\nConstraintQuery == " + constraint_arg;
+      con_index = (int)con_inv_names.size();
+      if (vsrmc_predicates_compile(m, local.c_str(), &w_con) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
   }
   if (simulate) {   // ≙ tlc2.TLC -simulate -depth N
@@ -529,6 +562,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  if (w_con && vsrmc_checker_constrain_attach(c, w_con, con_index) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   static const char* const MODULES[3] = {"VSR.tla", "VR_STATE_TRANSFER.tla", "VR_APP_STATE.tla"};
   std::printf("vsrmc: %s lowered: ReplicaCount=%d ClientCount=%d |Values|=%d StartViewOnTimerLimit=%d, %d permutation(s), "
               "invariant mask %d\n", MODULES[lay.module >= 0 && lay.module < 3 ? lay.module : 0], lay.replica_count, lay.client_count, lay.value_count, lay.start_view_on_timer_limit,
@@ -537,7 +574,8 @@ int main(int argc, char** argv) {
   auto t_chk = t0;
   vsrmc_level_info info;
   vsrmc_checker_status(c, &info);
-  if (recover_file.empty()) std::printf("Finished computing initial states: 1 distinct state generated.\n");
+  if (w_con) std::printf("Finished computing initial states: 1 state generated, %llu in the model of CONSTRAINT %s.\n", (unsigned long long)info.distinct, constraint_arg.c_str());
+  else if (recover_file.empty()) std::printf("Finished computing initial states: 1 distinct state generated.\n");
   else std::printf("Recovered from %s: level %d, %llu distinct states found, %llu states left on queue.\n", recover_file.c_str(), info.level,
                    (unsigned long long)info.distinct, (unsigned long long)info.n_new);
   int rc = 0;
@@ -579,6 +617,23 @@ int main(int argc, char** argv) {
   };
   if (dump && recover_file.empty() && !dump_level(1)) return 1;
   bool violated = false, deadlocked = false, probed_violation = false, incomplete = false;
+  // -constraint: the figures of every level the filter ran on (level 1 = Init), the run's total, a user's invariant that fails among the pruned states
+  bool con_no_room = false;
+  std::string con_reason;
+  unsigned long long con_pruned_total = 0;
+  int con_seen_level = 0, con_hit = -1, con_hit_level = 0;
+  uint64_t con_hit_fp = 0;
+  vsrmc_constraint_info con_info;
+  std::memset(&con_info, 0, sizeof(con_info));
+  auto con_collect = [&]() -> bool {                              // true: the newest filtered level is one not seen before (con_info holds it)
+    if (!w_con || vsrmc_checker_constraint_info(c, 0, &con_info) != 0 || con_info.level <= con_seen_level) return false;
+    con_seen_level = con_info.level;
+    con_pruned_total += (unsigned long long)con_info.pruned;
+    for (size_t k = 0; k < con_inv_names.size() && con_hit < 0; k++)
+      if (con_info.pruned_count[k]) { con_hit = (int)k; con_hit_level = con_info.level; con_hit_fp = con_info.pruned_min_fp_k[k]; }
+    return true;
+  };
+  con_collect();                                                  // (Init)
   unsigned long long cov[16] = {0};
   uint64_t viol_level = 0, viol_index = 0;
   int depth = info.level + info.reserved0;                        // (a recovered deep search: the levels beyond the stored one)
@@ -847,8 +902,10 @@ int main(int argc, char** argv) {
       if (rc != 0) break;
       if (step_hit >= 0) break;
     }
+    if (con_hit >= 0) break;                                      // (Init is out of model and violates a user's invariant)
     rc = vsrmc_checker_advance(c, &info, &probed, &what);
     if (rc != 0) break;
+    if (what == 4) { con_no_room = true; con_reason = vsrmc_last_error(); break; }   // a constraint is attached and the next level does not fit
     if (what == 3) {                                              // no new level: the deep search was re-based (the levels shrink again)
       if (!json) std::printf("Re-based(%d): %llu states regenerated into the record buffers (%llu launches, %.2f s); stored levels from here on.\n", info.level,
                              (unsigned long long)info.n_new, (unsigned long long)info.pending, info.seconds);
@@ -908,6 +965,9 @@ int main(int argc, char** argv) {
       where_json += "}";
     }
     if (json && step_report && step_scanned_this_step) where_json += ", " + step_json_of();
+    const bool con_new = con_collect();                           // the level this step stored and filtered (none: the step found no new state)
+    if (json && w_con)
+      where_json += ", \"kept\": " + std::to_string(con_new ? (unsigned long long)con_info.kept : 0ull) + ", \"pruned\": " + std::to_string(con_new ? (unsigned long long)con_info.pruned : 0ull);
     if (json && scanned_this_step)                                // (terminal / unsettled: of the level this step expanded, like deadlocks)
       std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu%s, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -924,7 +984,8 @@ int main(int argc, char** argv) {
       std::printf("Progress(%d): %llu states generated, %llu distinct states found, %llu states left on queue. (%.2f s)\n", info.level,
                   (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, dt);
     if (!dump_level(info.n_new)) { rc = -1; break; }
-    if (info.viol_mask) { violated = true; viol_level = (uint64_t)info.level; viol_index = info.viol_index; break; }
+    if (info.viol_mask) { violated = true; viol_level = (uint64_t)(w_con && con_new ? con_info.level : info.level); viol_index = info.viol_index; break; }
+    if (con_hit >= 0) break;
     if (check_deadlock && info.deadlocks) { deadlocked = true; break; }
     if (info.n_new == 0) break;
     checkpoint_now(info.level);
@@ -968,6 +1029,7 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> words(cap_w), off(viol_level + 2);
     std::vector<int32_t> acts(viol_level + 2);
     if ((probed_violation ? vsrmc_checker_probe_trace(c, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states)
+         : w_con          ? vsrmc_checker_trace_fp(c, (int32_t)viol_level, info.viol_fp, words.data(), cap_w, off.data(), acts.data(), off.size(), &n_states)   // (the violator may be out of model)
                           : vsrmc_checker_trace(c, (int32_t)viol_level, viol_index, words.data(), cap_w, off.data(), acts.data(), off.size(),
                                                 &n_states)) != 0) {
       std::printf("Error: %s\n", vsrmc_last_error());
@@ -1030,6 +1092,9 @@ int main(int argc, char** argv) {
       }
       exit_code = inv ? 12 : 0;
     }
+  } else if (con_hit >= 0) {                                    // a user's invariant that fails on a state the constraint pruned
+    std::printf("Error: Invariant %s is violated (by a state of level %d that is outside CONSTRAINT %s).\n", con_inv_names[con_hit].c_str(), con_hit_level, constraint_arg.c_str());
+    exit_code = print_behaviour_to(con_hit_level, con_hit_fp, false) ? 12 : 1;
   } else if (where_hit >= (int)n_reach) {                       // a user's invariant: reported like a built-in one
     std::printf("Error: Invariant %s is violated.\n", query_names[where_hit].c_str());
     exit_code = print_behaviour_to(wi_query.level, wi_query.min_fp[where_hit], false) ? 12 : 1;
@@ -1064,9 +1129,14 @@ int main(int argc, char** argv) {
     std::printf("Model checking INCOMPLETE at depth %d: the seen-set is more than 85 %% full and the device has no memory for a larger one "
                 "(no error has been found up to that depth).\n", depth);
     exit_code = 4;
+  } else if (con_no_room) {
+    std::printf("Model checking INCOMPLETE at depth %d: %s.\n", depth, con_reason.c_str());
+    exit_code = 4;
   } else if (info.n_new == 0) {
     std::printf("Model checking completed. No error has been found.\n");
   }
+  if (w_con && rc == 0)
+    std::printf("CONSTRAINT %s: %llu states were out of model and not explored; the distinct states below are the in-model ones.\n", constraint_arg.c_str(), con_pruned_total);
   if (terminal_report && rc == 0) {
     unsigned long long n_term = 0, n_uns = 0;
     for (const TermRow& r : term_rows) { n_term += r.n_terminal; n_uns += r.n_unsettled; }
@@ -1220,6 +1290,7 @@ int main(int argc, char** argv) {
   if (c) vsrmc_checker_destroy(c);
   if (w_all) vsrmc_where_destroy(w_all);
   if (w_query) vsrmc_where_destroy(w_query);
+  if (w_con) vsrmc_where_destroy(w_con);
   if (s_all) vsrmc_where_destroy(s_all);
   if (s_query) vsrmc_where_destroy(s_query);
   vsrmc_model_destroy(m);
