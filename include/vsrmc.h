@@ -384,6 +384,55 @@ int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, i
 int32_t vsrmc_checker_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_constraint_info* out);
 int32_t vsrmc_checker_constraint_pruned(vsrmc_checker* c, uint64_t* fps, uint64_t cap, uint64_t* n);
 
+/* ---- action constraints: which steps the search does not take (TLC's ACTION_CONSTRAINT) ---------------------------------
+ * One exported predicate P of a step program (vsrmc_step_predicates_compile, below) attached to a checker.  A transition (s, t) by an instance
+ * (parent, ordinal) is GENERATED and counted in `generated` and act_generated as ever.  P true: t is fingerprinted and claimed in the seen-set; a new t
+ * is written to the next level with s as its candidate parent (the min-key rule).  P false: the transition is BLOCKED — t is not fingerprinted into
+ * the seen-set and not written, and may still enter the model through a permitted transition of the same or a later level (what separates an action
+ * constraint from a state constraint, which judges t whatever led to it).  Init is not subject to it.  The parent pointer of every stored state is a
+ * permitted parent, and vsrmc_checker_trace / _trace_fp take permitted steps only: where several instances of one parent lead to one child, the smallest
+ * permitted ordinal is taken.  An instance whose action raises an evaluation error ends the run as without a constraint.  Deadlock stays "no successor
+ * generated".  [TLC-RECALLED: written from memory of tlc2.tool.ModelChecker.doNext, not pinned against a TLC run.]  Departure: TLC (recalled) checks the
+ * invariants on a successor it then discards; here the built-in invariants are evaluated on blocked successors only to COUNT them
+ * (blocked_violating, blocked_viol_mask, blocked_viol_min_fp) — no violation is reported for a state that is not in the model.  An ACTION_CONSTRAINT
+ * section of a cfg stays refused at load: the constraint is attached through this interface only.
+ * How: vsrmc_checker_step runs k_step_list, k_step_apply (the verdict) and k_step_expand (csrc/vsr_action_constrain.hpp) over slices of the newest level
+ *   in the place of k_expand; the level it leaves has k_expand's format (dense: no unused index), so every scan, trace and accessor works on it, and a
+ *   state constraint (vsrmc_checker_constrain_attach) may be attached beside it.  A checker without an action constraint runs the code it ran before.
+ *   vsrmc_checker_step_scan of a constrained checker judges the permitted transitions only: per slice the constraint's verdicts first (k_step_apply), the
+ *   permitted entries of the list kept (k_step_keep), then the caller's program over those — n_pairs, counts, minima, the witness ordinal and
+ *   vsrmc_checker_step_pairs are those of the constrained model, and the pair vsrmc_checker_step_successor gives is a permitted step.
+ *   A permitted trace costs two batch calls (vsrmc_expand_batch, vsrmc_step_batch) of one record per state of the path: a report's cost, not a hot path.
+ * vsrmc_checker_action_constrain_attach: accepted only on a checker at level 1 (fresh, or after vsrmc_checker_reset); starts the search over.  w == NULL
+ *   detaches, at any level, and starts the search over.  The program is copied; its device buffers are allocated once per attachment.
+ *   Refused: VSRMC_E_ARG for a state program (vsrmc_where_desc.step must be set), a program compiled for another model, a name_index the program
+ *   does not export, and a program that reads aux_svc or aux_client_acked, primed or not (outside VIEW: the copy of a state that arrived first would decide
+ *   which transitions are taken; under SYMMETRY the compiler already refuses value literals); VSRMC_E_STATE with exact_ties = 1, on a sharded checker
+ *   (world > 1), after level 1, with predicates attached by vsrmc_checker_deep_attach, and for a second attachment.
+ * While attached: vsrmc_checker_deepen, _probe, _probe2, _probe3, _deep_attach and _save are refused (VSRMC_E_STATE), and vsrmc_checker_advance stores
+ *   levels only — when the next level is not predicted to fit, or overflowed, it returns 0 with *what = 4 (vsrmc_check: stop_reason 5), as with a state
+ *   constraint.  Blocked successors take neither record room nor a seen-set slot: the prediction is not scaled for them and vsrmc_checker_room counts the
+ *   distinct states as the table's load.
+ * vsrmc_checker_action_constraint_info: the figures of the step that led INTO `level` (>= 2; 0 asks for the newest step, which may have found no state).
+ * (Test knobs: the environment variable VSRMC_ACTION_SLICE=N fixes the parents per slice at N — without it the first slice of a level is sized so that
+ *   the list cannot overflow and the later ones from the instances per parent seen so far, times 1.5; VSRMC_ACTION_LIST_CAP=N, read at attach, shortens
+ *   the instance list (default 2^22 entries, at least 64), so that slices overflow it and are listed again in halves.  They have no other use.) */
+typedef struct vsrmc_action_constraint_info {
+  int32_t level, k;                                /* the level the step led into; the exported predicate that is the constraint */
+  uint64_t parents;                                /* states expanded */
+  uint64_t pairs, permitted, blocked;              /* transitions generated = taken + not taken */
+  uint64_t blocked_act[16];                        /* blocked per action id */
+  uint64_t blocked_violating, blocked_viol_mask;   /* blocked successors that fail a built-in invariant; the or of their masks */
+  uint64_t blocked_min_fp, blocked_viol_min_fp;    /* the smallest PARENT fingerprint of a blocked pair / of one whose successor fails an invariant; ~0 if none */
+  uint64_t n_new;                                  /* new states the step wrote */
+  uint64_t slices, relisted, launches;             /* k_step_list launches; of them slices that overflowed the list and were listed again in halves; kernel launches in all */
+  double list_ms, verdict_ms, expand_ms;           /* HIP-event time of k_step_list, k_step_apply, k_step_expand, summed over the slices */
+} vsrmc_action_constraint_info;
+int32_t vsrmc_checker_action_constrain_attach(vsrmc_checker* c, const vsrmc_where* step_program, int32_t name_index);
+int32_t vsrmc_checker_action_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_action_constraint_info* out);
+/* the seen-set's load as the table shows it: slots that hold a fingerprint, of how many.  Counted on the host from a copy of the table (tests, reports). */
+int32_t vsrmc_checker_seen_set_load(vsrmc_checker* c, uint64_t* occupied, uint64_t* slots);
+
 /* ---- step predicates: user-written predicates over a state AND its successor, checked on every transition -------------------------
  * The safety half of PROPERTY: an action property [][P]_vars is a predicate over a (state, successor) pair.  The language of the state predicates
  * plus primed variables (rep_view_number'[r], Len(rep_log[r])', (...)', \A m \in DOMAIN messages', messages'[m]), UNCHANGED e and step_action (the

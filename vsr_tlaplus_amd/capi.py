@@ -62,6 +62,13 @@ class ConstraintInfo(C.Structure):
                 ("pruned_count", C.c_uint64 * 8), ("pruned_min_fp_k", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
 
 
+class ActionConstraintInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("k", C.c_int32), ("parents", C.c_uint64), ("pairs", C.c_uint64), ("permitted", C.c_uint64), ("blocked", C.c_uint64),
+                ("blocked_act", C.c_uint64 * 16), ("blocked_violating", C.c_uint64), ("blocked_viol_mask", C.c_uint64), ("blocked_min_fp", C.c_uint64),
+                ("blocked_viol_min_fp", C.c_uint64), ("n_new", C.c_uint64), ("slices", C.c_uint64), ("relisted", C.c_uint64), ("launches", C.c_uint64),
+                ("list_ms", C.c_double), ("verdict_ms", C.c_double), ("expand_ms", C.c_double)]
+
+
 class StepInfo(C.Structure):
     _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("n_pairs", C.c_uint64), ("n_err", C.c_uint64),
                 ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8), ("min_index", C.c_uint64 * 8), ("min_ordinal", C.c_uint32 * 8),
@@ -162,6 +169,9 @@ SYMBOLS = {
     "vsrmc_checker_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
     "vsrmc_checker_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ConstraintInfo)]),
     "vsrmc_checker_constraint_pruned": (C.c_int32, [V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_action_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
+    "vsrmc_checker_action_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ActionConstraintInfo)]),
+    "vsrmc_checker_seen_set_load": (C.c_int32, [V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vsrmc_step_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_predicates_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_batch": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, V, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -437,6 +437,7 @@ class ModelChecker:
         self._deep = None                                            # (state Where, step Where) of deep_attach, or None
         self._deep_seen = set()                                      # (level, probed) pairs run(deep=True) has looked at
         self._constraint = None                                      # (Where, k) of constrain(), or None
+        self._action_constraint = None                               # (step Where, k) of action_constrain(), or None
         self.stopped = None                                          # the reason advance() gave for ("stopped", ..)
         self._pruned_checked = 0                                     # the newest filtered level run(never=..) has looked at
         o = capi.Options()
@@ -519,6 +520,63 @@ class ModelChecker:
         self._constraint = (where, k)
         self._fresh()
         self._after_init_filter()
+
+    def action_constrain(self, step_where, name=None):
+        """Attach an action constraint (TLC's ACTION_CONSTRAINT; vsrmc_checker_action_constrain_attach): the exported predicate `name` (a name or a number;
+        None: the program's only one) of the STEP program `step_where` (Model.compile_step_predicates).  A transition that fails it is generated and
+        counted but not taken: its successor is neither put into the seen-set nor stored, and may still be reached by a permitted transition.  Init is
+        not subject to it.  At level 1 only (a fresh checker, or after reset()); step_where=None detaches, at any level, and starts over.  A state constraint
+        (constrain) may be attached beside it.  While attached, levels are stored only (run(): "constraint-out-of-room" when the next one does not fit);
+        deepen / probe / deep_attach / save are refused; every trace takes permitted steps only, and step_scan / step_never / step_reach judge the
+        permitted transitions only (a blocked one is neither counted nor listed, and is never a witness)."""
+        if step_where is None:
+            check(capi.load().vsrmc_checker_action_constrain_attach(self._h, None, 0))
+            self._action_constraint = None
+            self._fresh()
+            self._after_init_filter()
+            return
+        if name is None:
+            if len(step_where.names) != 1:
+                raise ValueError("the program exports %d predicates: name the action constraint" % len(step_where.names))
+            name = 0
+        k = name if isinstance(name, int) else step_where.names.index(name)
+        check(capi.load().vsrmc_checker_action_constrain_attach(self._h, step_where._h, k))
+        self._action_constraint = (step_where, k)
+        self._fresh()
+        self._after_init_filter()
+
+    def action_constraint_results(self, level=None):
+        """The figures of the steps taken under the action constraint (vsrmc_checker_action_constraint_info) -> [dict(level, k, parents, pairs, permitted,
+        blocked, blocked_act={action name: n}, blocked_violating, blocked_viol_mask, blocked_min_fp, blocked_viol_min_fp, n_new, slices, relisted,
+        launches, list_ms, verdict_ms, expand_ms)], the step into level 2 first; level=L: the step into level L (0: the newest step, which may have
+        found nothing).  Fingerprints are the PARENT's, None where there is no such pair."""
+        if self._action_constraint is None:
+            raise ValueError("no action constraint attached (action_constrain)")
+        none = (1 << 64) - 1
+
+        def one(lv):
+            ai = capi.ActionConstraintInfo()
+            check(capi.load().vsrmc_checker_action_constraint_info(self._h, lv, C.byref(ai)))
+            d = {n: getattr(ai, n) for n, _ in ai._fields_ if n != "blocked_act"}
+            d["blocked_act"] = {ACTION_NAMES[a]: int(ai.blocked_act[a]) for a in range(16) if ai.blocked_act[a]}
+            for f in ("blocked_min_fp", "blocked_viol_min_fp"):
+                d[f] = None if d[f] == none else int(d[f])
+            return d
+        if level is not None:
+            return one(level)
+        out, lv = [], 2
+        while True:
+            try:
+                out.append(one(lv))
+            except VsrmcError:
+                return out
+            lv += 1
+
+    def seen_set_load(self):
+        """(occupied slots, slots) of the seen-set, counted from a copy of the table (vsrmc_checker_seen_set_load)."""
+        occ, slots = C.c_uint64(), C.c_uint64()
+        check(capi.load().vsrmc_checker_seen_set_load(self._h, C.byref(occ), C.byref(slots)))
+        return occ.value, slots.value
 
     def constraint_results(self, level=None):
         """The figures of the filtered levels (vsrmc_checker_constraint_info) -> [dict(level, k, n_states, kept, pruned, kept_xor, kept_sum, kept_max_bag,

@@ -1,0 +1,329 @@
+// host_action_constrain.hpp — action constraints: the host side of k_step_expand (vsr_action_constrain.hpp) — attaching one exported
+// predicate of a compiled step program to a checker, the level step that takes only the permitted transitions (phase_expand_gated, in the place of
+// phase_expand), the per-level figures, and the trace that takes only permitted steps (included by vsrmc.hip: one translation unit, the sections share
+// its anonymous-namespace helpers).
+#pragma once
+
+struct vsrmc_action_constraint {
+  vsrmc_where prog;                    // a copy: the caller may destroy its own
+  int k = 0;                           // the exported predicate that is the constraint
+  // device buffers, allocated once per attachment
+  u32* d_prog = nullptr;               // the program (uploaded once)
+  u64* d_list = nullptr;               // the instance list of one slice (list_cap entries) ..
+  u32* d_rows = nullptr;               // .. the verdict beside every entry ..
+  u32* d_live = nullptr;               // .. and one word per parent of the slice (live_cap of them): has it an instance?
+  StepCtl* d_sctl = nullptr;
+  ActionCtl* d_actl = nullptr;
+  u64 list_cap = 0, live_cap = 0;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  std::vector<vsrmc_action_constraint_info> levels;   // [level]: the figures of the step INTO that level (levels 0 and 1 unused)
+  int newest = 0;                      // the level the last step led into
+};
+
+namespace {
+
+enum : u64 { ACTION_LIST_CAP = (u64)1 << 22 };
+
+void action_constraint_free(vsrmc_checker* c) {
+  vsrmc_action_constraint* a = c->action_constraint;
+  if (!a) return;
+  for (void* p : {(void*)a->d_prog, (void*)a->d_list, (void*)a->d_rows, (void*)a->d_live, (void*)a->d_sctl, (void*)a->d_actl})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : a->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete a;
+  c->action_constraint = nullptr;
+}
+
+// a search that starts over (checker_seed): the attachment stays, its results go.  Init is not subject to an action constraint: no transition leads to it.
+void action_constraint_restart(vsrmc_checker* c) {
+  if (!c->action_constraint) return;
+  c->action_constraint->levels.clear();
+  c->action_constraint->newest = 0;
+}
+
+const vsrmc_where* action_constraint_program(const vsrmc_checker* c, int* k) {
+  if (!c->action_constraint) return nullptr;
+  *k = c->action_constraint->k;
+  return &c->action_constraint->prog;
+}
+
+// phase 1 of a level with an action constraint attached, in the place of phase_expand (unsharded single-pass levels only: the attachment refuses the
+// rest).  Slices of the current level through k_step_list, k_step_apply and k_step_expand; the control block is read back once, at the end.  Leaves
+// c->h, c->nx_n and c->nx_w as phase_expand does, so that phase_commit, constrain_level and find_fp_newest run unchanged.
+int phase_expand_gated(vsrmc_checker* c) {
+  vsrmc_action_constraint* a = c->action_constraint;
+  const Model& M = c->model.M;
+  HIPCHK(hipSetDevice(c->opt.device));
+  if (c->level + 1 >= 511) return fail(VSRMC_E_REP, "more than 510 BFS levels");
+  c->t_level0 = now_s();
+  c->expand_ms = c->materialize_ms = 0;
+  std::memset(&c->h, 0, sizeof(c->h));
+  c->h.viol_fp = ~(u64)0;
+  c->level_fused = true;
+  c->nx_n = c->nx_w = 0;
+  c->full_recoverable = false;
+  ActionCtl ah;
+  std::memset(&ah, 0, sizeof(ah));
+  ah.blocked_min_pfp = ah.blocked_viol_min_pfp = ~(u64)0;
+  StepCtl sh;
+  std::memset(&sh, 0, sizeof(sh));
+  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) sh.min_fp[k] = ~(u64)0;
+  HIPCHK(hipMemcpyAsync(c->ctl, &c->h, sizeof(c->h), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(a->d_actl, &ah, sizeof(ah), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(a->d_sctl, &sh, sizeof(sh), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));                         // (the sources are pageable host memory on this frame)
+  auto* const list_kernel = M.model_id == 1 ? k_step_list<1> : M.model_id == 2 ? k_step_list<2> : k_step_list<0>;   // (where_fits at attach: the program is this model's)
+  auto* const apply_kernel = M.model_id == 1 ? k_step_apply<1> : M.model_id == 2 ? k_step_apply<2> : k_step_apply<0>;
+  auto* const expand_kernel = M.model_id == 1 ? k_step_expand<1> : M.model_id == 2 ? k_step_expand<2> : k_step_expand<0>;
+  const int nxt = c->cur ^ 1;
+  const u64 n = c->n_frontier, list_cap = a->list_cap;
+  const u64 nx_wcap = c->words_cap(nxt) > 256 ? c->words_cap(nxt) - 256 : 0;   // (a margin of one record: the writer copies the parent's words before it patches them)
+  // the first slice cannot overflow the list even if every ordinal of every parent were enabled; the later ones are sized from the instances per parent the
+  // slices before them showed (the largest mean of any slice of this level), times 1.5 — and a slice that overflows all the same is listed again in halves
+  // before anything of it is applied
+  const int bag = (c->bag_known && c->cur_max_bag) ? (int)std::min<u64>(c->cur_max_bag, (u64)M.max_bag) : M.max_bag;
+  u64 slice = std::max<u64>(1, list_cap / (u64)std::max(1, ord_count(M, bag)));
+  // TEST KNOB (documented in include/vsrmc.h): parents per slice, fixed (no adaptation)
+  bool fixed_slice = false;
+  if (const char* e = std::getenv("VSRMC_ACTION_SLICE")) { slice = std::max<u64>(1, std::strtoull(e, nullptr, 10)); fixed_slice = true; }
+  slice = std::min<u64>(slice, a->live_cap);
+  const u64 slice0 = slice;
+  double ipp_max = 0, list_ms = 0, verdict_ms = 0, expand_ms = 0;
+  u64 scanned = 0, slices = 0, relisted = 0, launches = 0;
+  bool timed = false;                                              // events 2..5 hold a slice whose kernel times have not been read yet
+  auto collect = [&]() -> int {
+    if (!timed) return 0;
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a->ev[2], a->ev[3]));
+    verdict_ms += (double)ms;
+    HIPCHK(hipEventElapsedTime(&ms, a->ev[4], a->ev[5]));
+    expand_ms += (double)ms;
+    timed = false;
+    return 0;
+  };
+  for (u64 pos = 0; pos < n;) {
+    const u64 end = std::min<u64>(n, pos + slice);
+    HIPCHK(hipMemsetAsync(a->d_sctl, 0, 16, c->stream));           // n_list, scanned: of this slice
+    HIPCHK(hipMemsetAsync(a->d_live, 0, (end - pos) * 4, c->stream));
+    const unsigned grid_l = (unsigned)std::max<u64>(1, std::min<u64>((end - pos + 255) / 256, (u64)c->num_cus * 8));
+    HIPCHK(hipEventRecord(a->ev[0], c->stream));
+    hipLaunchKernelGGL(list_kernel, dim3(grid_l), dim3(256), 0, c->stream, M, (const u64*)c->words[c->cur], (const u64*)c->off[c->cur], pos, end, a->d_list, list_cap, a->d_sctl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(a->ev[1], c->stream));
+    u64 head[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(head, a->d_sctl, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int rc = collect();                                            // (the slice before this one has finished as well)
+    if (rc) return rc;
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
+    list_ms += (double)ms;
+    slices++;
+    launches++;
+    if (head[0] > list_cap) {                                      // more instances than the list holds: the same parents again, half at a time, nothing of them applied
+      if (end - pos == 1) return fail(VSRMC_E_REP, "action constraint: one record has " + std::to_string(head[0]) + " enabled instances, the list holds " + std::to_string(list_cap));
+      slice = std::max<u64>(1, (end - pos) / 2);
+      relisted++;
+      continue;
+    }
+    scanned += head[1];
+    if (head[0]) {
+      const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)c->num_cus * 8));
+      HIPCHK(hipEventRecord(a->ev[2], c->stream));
+      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)a->d_prog, (int)a->prog.prog.names.size(), (const u64*)c->words[c->cur],
+                         (const u64*)c->off[c->cur], (const u64*)nullptr, (const u64*)a->d_list, head[0], a->d_sctl, (u64*)nullptr, (u64)0, a->d_rows);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(a->ev[3], c->stream));
+      HIPCHK(hipEventRecord(a->ev[4], c->stream));
+      hipLaunchKernelGGL(expand_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u64*)c->words[c->cur], (const u64*)c->off[c->cur], (const u64*)a->d_list,
+                         (const u32*)a->d_rows, head[0], a->k, c->level + 1, pos, c->table, c->tmask, c->words[nxt], nx_wcap, c->off[nxt], c->opt.frontier_states,
+                         c->lvl_fp, c->ctl, a->d_actl, a->d_live);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(a->ev[5], c->stream));
+      timed = true;
+      launches += 2;
+    }
+    if (fixed_slice) {
+      slice = std::min<u64>(slice0, slice * 2);                    // (a slice that was halved grows back once the dense region is behind)
+    } else {
+      ipp_max = std::max(ipp_max, (double)head[0] / (double)(end - pos));
+      slice = std::max<u64>(1, std::min<u64>(a->live_cap, (u64)((double)list_cap / (ipp_max * 1.5 + 1.0))));
+    }
+    pos = end;
+  }
+  HIPCHK(hipMemcpyAsync(&c->h, c->ctl, sizeof(c->h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&ah, a->d_actl, sizeof(ah), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&sh, a->d_sctl, sizeof(sh), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int rc = collect();
+  if (rc) return rc;
+  c->expand_ms = list_ms + verdict_ms + expand_ms;
+  if (scanned != c->n_valid) { c->failed = 1; return fail(VSRMC_E_HIP, "k_step_list: scanned " + std::to_string(scanned) + " records of " + std::to_string(c->n_valid)); }
+  if (sh.n_internal) { c->failed = 1; return fail(VSRMC_E_HIP, "k_step_apply: " + std::to_string(sh.n_internal) + " listed instances are not enabled (guard_slot_pre and gen disagree)"); }
+  c->h.deadlocks = scanned - ah.live_parents;
+  if (!c->h.err && c->h.full) {                                    // the record buffers ran out: with a constraint attached vsrmc_checker_advance ends the run there
+    c->h.err = ERR_FRONTIER_FULL;
+    c->h.err_info = c->h.full_info << 16;
+    c->full_recoverable = c->h.ties == 0;
+    if (c->full_recoverable) { c->full_h = c->h; c->full_ms = c->expand_ms; c->full_t0 = c->t_level0; }
+  }
+  if (c->h.err) return level_error(c, c->h, c->level + 1);
+  c->nx_n = c->h.n_new;                                            // (dense: the index range is the number of states)
+  c->nx_w = c->h.words_new;
+  if (c->h.ties) {
+    c->failed = 1;
+    return fail(VSRMC_E_STATE, "two successors of one level share a VIEW fingerprint but differ in the aux variables (SURVEY F2); the single-pass scheme cannot arbitrate, "
+                               "and an action constraint needs it");
+  }
+  vsrmc_action_constraint_info ai;
+  std::memset(&ai, 0, sizeof(ai));
+  ai.level = c->level + 1;
+  ai.k = a->k;
+  ai.parents = scanned;
+  ai.pairs = c->h.generated;
+  ai.blocked = ah.blocked;
+  ai.permitted = c->h.generated - ah.blocked;
+  for (int i = 0; i < 16; i++) ai.blocked_act[i] = ah.blocked_act[i];
+  ai.blocked_violating = ah.blocked_violating;
+  ai.blocked_viol_mask = ah.blocked_viol_mask;
+  ai.blocked_min_fp = ah.blocked_min_pfp;
+  ai.blocked_viol_min_fp = ah.blocked_viol_min_pfp;
+  ai.n_new = c->h.n_written;
+  ai.slices = slices; ai.relisted = relisted; ai.launches = launches;
+  ai.list_ms = list_ms; ai.verdict_ms = verdict_ms; ai.expand_ms = expand_ms;
+  if (a->levels.size() <= (size_t)ai.level) a->levels.resize((size_t)ai.level + 1);
+  a->levels[(size_t)ai.level] = ai;
+  a->newest = ai.level;
+  return 0;
+}
+
+// The behaviour along the fingerprints a walk through the seen-set gave (fps[0] = Init's), taking PERMITTED steps only: k_replay takes the smallest ordinal
+// whose successor has the next fingerprint, permitted or not, so with an action constraint attached the path is rebuilt here instead — every state of it
+// through the expand batch (successor fingerprints) and the step batch (verdicts), the smallest permitted ordinal that leads to the next fingerprint taken.
+// Such an ordinal exists: the parent pointer of a stored state was written by a permitted transition.  Cost: per state of the path two batch calls of one
+// record (vsrmc_expand_batch, vsrmc_step_batch), each with its own device allocations, copies and launches — a report's path, tens of states, not a hot path.
+int action_constraint_trace(vsrmc_checker* c, const std::vector<u64>& fps, u64* words, u64 cap_words, u64* off, int32_t* actions, u64 cap_states, u64* n_states) {
+  const vsrmc_action_constraint* a = c->action_constraint;
+  const Model& M = c->model.M;
+  const u64 level = fps.size();
+  if (cap_states < level + 1) return fail(VSRMC_E_ARG, "state buffers too small");
+  std::vector<u64> cur;
+  init_record_wire(M, cur);
+#ifdef VSRMC_TEST_HOOKS
+  if (g_test_replay_start) cur.assign(g_test_replay_start, g_test_replay_start + M.h0 + hdr_nmsg(g_test_replay_start[0]));   // (a seeded search: as replay_path)
+#endif
+  u64 pos = 0;
+  for (u64 t = 0; t < level; t++) {
+    if (t > 0) {
+      const u64 poff[2] = {0, (u64)cur.size()};
+      const u64 cap = (u64)ord_count(M, hdr_nmsg(cur[0])) + 1, capw = cap * 256;
+      std::vector<u64> ow(capw), om(cap * 8), rows(cap * 5);
+      u64 n_out = 0, w_out = 0, n_rows = 0;
+      int rc = vsrmc_expand_batch(&c->model, c->opt.device, cur.data(), poff, 1, ow.data(), capw, om.data(), cap, &n_out, &w_out);
+      if (rc) return rc;
+      rc = vsrmc_step_batch(&c->model, c->opt.device, &a->prog, cur.data(), poff, 1, rows.data(), cap, &n_rows);
+      if (rc) return rc;
+      u64 at = n_out;
+      for (u64 k = 0; k < n_out && at == n_out; k++) {             // (both batches are in ordinal order)
+        if (om[8 * k + 6] || om[8 * k + 3] != fps[t]) continue;
+        for (u64 q = 0; q < n_rows; q++)
+          if (rows[5 * q + 1] == om[8 * k + 1] && !rows[5 * q + 4] && ((rows[5 * q + 3] >> a->k) & 1)) { at = k; break; }
+      }
+      if (at == n_out) return fail(VSRMC_E_STATE, "action constraint: a state of the path has no permitted step to the next fingerprint");
+      const u64 wo = om[8 * at + 7], len = (u64)M.h0 + (u64)hdr_nmsg(ow[wo]);
+      cur.assign(&ow[wo], &ow[wo] + len);
+      actions[t] = (int32_t)om[8 * at + 2];
+    } else {
+      actions[0] = 0;
+    }
+    if (pos + cur.size() > cap_words) return fail(VSRMC_E_ARG, "word buffer too small");
+    off[t] = pos;
+    std::copy(cur.begin(), cur.end(), words + pos);
+    pos += cur.size();
+  }
+  off[level] = pos;
+  *n_states = level;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t vsrmc_checker_action_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, int32_t name_index) {
+  if (!c) return fail(VSRMC_E_ARG, "NULL argument");
+  if (c->opt.world > 1) return fail(VSRMC_E_STATE, "action constraint: sharded checkers (world > 1) are not constrained");
+  if (c->opt.exact_ties) return fail(VSRMC_E_STATE, "action constraint: exact_ties = 1 (the two-kernel scheme claims the seen-set before a successor is materialised; the gate needs the single-pass scheme)");
+  if (!w) {                                                        // detach, at any level: the search starts over unconstrained
+    if (!c->action_constraint) return 0;
+    HIPCHK(hipSetDevice(c->opt.device));
+    action_constraint_free(c);
+    return checker_seed(c);
+  }
+  if (c->level != 1 || c->total_generated != 0 || c->failed || c->deep || c->deep_regen_done)
+    return fail(VSRMC_E_STATE, "action constraint: attached at level 1 only, to a fresh checker or after vsrmc_checker_reset (every transition of the search is subject to it)");
+  if (c->deep_attach) return fail(VSRMC_E_STATE, "action constraint: predicates are attached for the levels beyond the record buffers (vsrmc_checker_deep_attach): those levels are not constrained");
+  if (!w->prog.step) return fail(VSRMC_E_ARG, "action constraint: a state program (vsrmc_where_compile) judges a state; an action constraint is a step predicate (vsrmc_step_predicates_compile: vsrmc_where_desc.step)");
+  if (!where_fits(w, c->model.M, c->model.symmetry)) return fail(VSRMC_E_ARG, "action constraint: compiled for another model");
+  if (name_index < 0 || (size_t)name_index >= w->prog.names.size()) return fail(VSRMC_E_ARG, "action constraint: the program exports no predicate of that index");
+  if (constraint_reads_aux(w->prog))
+    return fail(VSRMC_E_ARG, "action constraint: the program reads aux_svc or aux_client_acked (primed or not), which are outside VIEW: of the copies of one state the one that "
+                             "arrived first would decide which transitions are taken");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "action constraint: one is attached already (NULL detaches it)");
+  HIPCHK(hipSetDevice(c->opt.device));
+  vsrmc_action_constraint* a = new vsrmc_action_constraint();
+  a->prog = *w;
+  a->k = name_index;
+  a->list_cap = ACTION_LIST_CAP;
+  // TEST KNOB (documented in include/vsrmc.h): a shorter instance list, so that slices of a small level overflow it and are listed again in halves
+  if (const char* e = std::getenv("VSRMC_ACTION_LIST_CAP")) a->list_cap = std::max<u64>(64, std::min<u64>(ACTION_LIST_CAP, std::strtoull(e, nullptr, 10)));
+  a->live_cap = std::max<u64>(64, std::min<u64>(a->list_cap, c->opt.frontier_states));
+  c->action_constraint = a;
+  hipError_t e = hipMalloc((void**)&a->d_prog, WHERE_MAX_OPS * sizeof(u32));
+  if (e == hipSuccess) e = hipMalloc((void**)&a->d_list, a->list_cap * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&a->d_rows, a->list_cap * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&a->d_live, a->live_cap * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&a->d_sctl, sizeof(StepCtl));
+  if (e == hipSuccess) e = hipMalloc((void**)&a->d_actl, sizeof(ActionCtl));
+  for (hipEvent_t& ev : a->ev)
+    if (e == hipSuccess) e = hipEventCreate(&ev);
+  if (e == hipSuccess) e = hipMemcpy(a->d_prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    action_constraint_free(c);
+    return fail(VSRMC_E_HIP, std::string("action constraint: ") + hipGetErrorString(e));
+  }
+  return checker_seed(c);                                          // (a fresh search: the state constraint, if one is attached, evaluates Init again)
+}
+
+int32_t vsrmc_checker_action_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_action_constraint_info* out) {
+  if (!c || !out) return fail(VSRMC_E_ARG, "NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  const vsrmc_action_constraint* a = c->action_constraint;
+  if (!a) return fail(VSRMC_E_STATE, "no action constraint attached (vsrmc_checker_action_constrain_attach)");
+  if (level == 0) level = a->newest;                               // the level the last step led into
+  if (level < 2 || (size_t)level >= a->levels.size() || a->levels[(size_t)level].level != level) return fail(VSRMC_E_ARG, "action constraint: no step has led into that level");
+  *out = a->levels[(size_t)level];
+  return 0;
+}
+
+// the seen-set's load as the table itself shows it: the slots that hold a fingerprint, counted on the host from a copy (a figure for tests and reports, not for a
+// hot path: the whole table crosses the bus)
+int32_t vsrmc_checker_seen_set_load(vsrmc_checker* c, uint64_t* occupied, uint64_t* slots) {
+  if (!c || !occupied || !slots) return fail(VSRMC_E_ARG, "NULL argument");
+  *occupied = 0;
+  *slots = c->tmask + 1;
+  HIPCHK(hipSetDevice(c->opt.device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const u64 window = (u64)1 << 20;
+  std::vector<Slot> buf((size_t)std::min<u64>(window, *slots));
+  for (u64 first = 0; first < *slots; first += window) {
+    const u64 n = std::min<u64>(window, *slots - first);
+    HIPCHK(hipMemcpy(buf.data(), c->table + first, n * sizeof(Slot), hipMemcpyDeviceToHost));
+    for (u64 i = 0; i < n; i++) *occupied += buf[i].fp != 0;
+  }
+  return 0;
+}
+
+}  // extern "C"

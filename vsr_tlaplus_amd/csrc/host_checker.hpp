@@ -16,6 +16,7 @@ struct PassDst {            // where a pass writes (records, refs, fingerprints)
 struct DeepLevelRec { u64 n_new = 0, n_local = 0, generated = 0, max_bag = 0, frontier = 0; };   // n_local: this rank's share (unsharded: all)   // a level that exists in the seen-set only (vsr_deep.hpp)
 struct vsrmc_deep_attach;    // a user's predicates on the levels beyond the record buffers (host_deep_where.hpp)
 struct vsrmc_constraint;     // a user's state constraint, applied to every level right after it is committed (host_constrain.hpp)
+struct vsrmc_action_constraint;   // a user's action constraint: the level step takes the permitted transitions only (host_action_constrain.hpp)
 struct vsrmc_checker {
   vsrmc_model model;
   vsrmc_options opt;
@@ -126,6 +127,7 @@ struct vsrmc_checker {
   vsrmc_deep_attach* deep_attach = nullptr;   // vsrmc_checker_deep_attach (host_deep_where.hpp): programs, persistent device buffers, per-level results; not part of a checkpoint
   u64 table_pruned = 0;                       // states the constraint pruned since the search started: no distinct states, but each keeps its seen-set slot (vsrmc_checker_room)
   vsrmc_constraint* constraint = nullptr;     // vsrmc_checker_constrain_attach (host_constrain.hpp): the program, its device buffers, per-level results; a checkpoint is refused while attached
+  vsrmc_action_constraint* action_constraint = nullptr;   // vsrmc_checker_action_constrain_attach (host_action_constrain.hpp): the same for a step program; step_local then runs phase_expand_gated
 #ifdef VSRMC_TEST_HOOKS
   // TEST HOOK (host_test_seed.hpp): the wire records a seeded search started from, by fingerprint — its traces start at one of them, not at Init
   std::vector<std::pair<u64, u64>> test_seed_index;   // (fingerprint, record number), ascending
@@ -151,6 +153,13 @@ int constraint_restart(vsrmc_checker* c);
 void constraint_free(vsrmc_checker* c);
 int constraint_beyond(const vsrmc_checker* c);
 double constraint_write_ratio(const vsrmc_checker* c);   // states k_expand wrote per state the filter kept, in the newest filtered level (1 without a constraint)
+// host_action_constrain.hpp (defined there, as above): phase 1 of a level through the gate, in the place of phase_expand; a search that starts over keeps the
+// attachment and forgets its results; a checker that is destroyed frees it; the behaviour along a walk's fingerprints by permitted steps only
+int phase_expand_gated(vsrmc_checker* c);
+void action_constraint_restart(vsrmc_checker* c);
+void action_constraint_free(vsrmc_checker* c);
+int action_constraint_trace(vsrmc_checker* c, const std::vector<u64>& fps, u64* words, u64 cap_words, u64* off, int32_t* actions, u64 cap_states, u64* n_states);
+const vsrmc_where* action_constraint_program(const vsrmc_checker* c, int* k);   // the attached step program and its exported predicate; NULL without an attachment
 typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*, u64, u64*, u64, LevelCtl*, int, int, u64*, u64, u32, u64*,
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,
@@ -417,6 +426,7 @@ int checker_seed(vsrmc_checker* c) {
   c->probe_viol_level = 0;
   deep_attach_restart(c);
   c->table_pruned = 0;
+  action_constraint_restart(c);
   return constraint_restart(c);                                 // (no constraint attached: nothing)
 }
 }  // namespace
@@ -923,7 +933,7 @@ int find_fp_newest(vsrmc_checker* c, u64 fp, u64* idx) {
 extern "C" {
 
 static int32_t step_local(vsrmc_checker* c, vsrmc_level_info* info) {
-  int rc = phase_expand(c, nullptr);
+  int rc = c->action_constraint ? phase_expand_gated(c) : phase_expand(c, nullptr);   // (an action constraint: single-pass levels only, refused at attach otherwise)
   if (!rc && c->opt.exact_ties) rc = phase_materialize_local(c);
   if (rc) {   // like a TLC evaluation error: the run aborts, the partial level is not committed
     std::memset(info, 0, sizeof(*info));

@@ -40,6 +40,7 @@ int32_t vsrmc_checker_save(vsrmc_checker* c, const char* path) {
   if (!c || !path) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->failed) return fail(VSRMC_E_STATE, "the checker stopped on an error");
   if (c->constraint) return fail(VSRMC_E_STATE, "checkpoint: a constraint is attached (vsrmc_checker_constrain_attach); a checkpoint does not name it, and a recovery would go on unconstrained");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "checkpoint: an action constraint is attached (vsrmc_checker_action_constrain_attach); a checkpoint does not name it, and a recovery would go on unconstrained");
   if (c->opt.world > 1 && c->opt.exact_ties) return fail(VSRMC_E_STATE, "checkpoints of sharded exact-mode checkers are not supported");
   // (a sharded search beyond its record buffers: the rank's winner set travels in a section of its own behind the frontier, the level loop's own state —
   // the run's totals, the violation — in a sidecar the loop writes: vsrmc_shard_loop_save)
@@ -513,6 +514,7 @@ int32_t vsrmc_checker_trace_fp(vsrmc_checker* c, int32_t level, uint64_t fp, uin
     g_test_replay_start = c->test_seed_words.data() + c->test_seed_off[it->second];
   }
 #endif
+  if (c->action_constraint) return action_constraint_trace(c, fps, words, cap_words, off, actions, cap_states, n_states);   // (k_replay takes the smallest ordinal, permitted or not)
   return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
 }
 
@@ -534,6 +536,7 @@ void vsrmc_checker_destroy(vsrmc_checker* c) {
   (void)hipSetDevice(c->opt.device);
   deep_attach_free(c);
   constraint_free(c);
+  action_constraint_free(c);
   if (c->table) (void)hipFree(c->table);
   for (int b = 0; b < 2; b++) {
     if (c->words[b]) (void)(((c->host_frontier >> b) & 1) ? hipHostFree(c->words[b]) : hipFree(c->words[b]));

@@ -329,6 +329,7 @@ int32_t vsrmc_checker_deep_attach(vsrmc_checker* c, const vsrmc_where* state_pro
     return 0;
   }
   if (c->constraint) return fail(VSRMC_E_STATE, "deep predicates: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "deep predicates: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (state_prog && state_prog->prog.step) return fail(VSRMC_E_ARG, "deep predicates: a step program in the state position");
   if (step_prog && !step_prog->prog.step) return fail(VSRMC_E_ARG, "deep predicates: a state program in the step position");
   if ((state_prog && !where_fits(state_prog, c->model.M, c->model.symmetry)) || (step_prog && !where_fits(step_prog, c->model.M, c->model.symmetry)))

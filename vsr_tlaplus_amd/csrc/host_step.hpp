@@ -21,9 +21,13 @@ struct StepBufs {
   u64 *list = nullptr, *hits = nullptr;
   StepCtl* ctl = nullptr;
   u32 *prog = nullptr, *rows = nullptr;
+  // a constrained checker's scan: the constraint's program, its verdicts, its counters (not reported), the permitted entries of the list and their number
+  u32 *gate_prog = nullptr, *gate_rows = nullptr;
+  StepCtl* gate_ctl = nullptr;
+  u64 *kept = nullptr, *n_kept = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   ~StepBufs() {
-    for (void* p : {(void*)list, (void*)hits, (void*)ctl, (void*)prog, (void*)rows})
+    for (void* p : {(void*)list, (void*)hits, (void*)ctl, (void*)prog, (void*)rows, (void*)gate_prog, (void*)gate_rows, (void*)gate_ctl, (void*)kept, (void*)n_kept})
       if (p) (void)hipFree(p);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -40,8 +44,11 @@ u64 step_slice_default(const Model& M, int bag_bound, u64 list_cap) {
 
 // the records refs[lo, hi) through both kernels, slice by slice.  The device counter of the instance list is checked after every k_step_list: a slice
 // that offered more than the list holds is run again in two halves, nothing of it having been applied.
+// `gate` (a checker with an action constraint attached): exported predicate gate_k of that step program says which transitions the model
+// takes.  Every slice's list then goes through k_step_apply with the GATE's program first and through k_step_keep, and `w` runs over the permitted
+// instances only: counts, minima, hits and rows are those of the constrained model.  apply_ms then holds all three launches of a slice.
 int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stream, const u64* d_words, const u64* d_refs, const u64* d_fps, u64 lo, u64 hi,
-             u64 slice, u64 list_cap, u64 hit_cap, bool want_rows, StepRun* out) {
+             u64 slice, u64 list_cap, u64 hit_cap, bool want_rows, StepRun* out, const vsrmc_where* gate = nullptr, int gate_k = 0) {
   StepBufs b;
   hit_cap = d_fps ? std::max<u64>(1, hit_cap) : 1;
   HIPCHK(hipMalloc((void**)&b.list, list_cap * 8));
@@ -49,6 +56,15 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
   HIPCHK(hipMalloc((void**)&b.ctl, sizeof(StepCtl)));
   HIPCHK(hipMalloc((void**)&b.prog, WHERE_MAX_OPS * sizeof(u32)));
   if (want_rows) HIPCHK(hipMalloc((void**)&b.rows, list_cap * 4));
+  if (gate) {
+    HIPCHK(hipMalloc((void**)&b.gate_prog, WHERE_MAX_OPS * sizeof(u32)));
+    HIPCHK(hipMalloc((void**)&b.gate_rows, list_cap * 4));
+    HIPCHK(hipMalloc((void**)&b.gate_ctl, sizeof(StepCtl)));
+    HIPCHK(hipMalloc((void**)&b.kept, list_cap * 8));
+    HIPCHK(hipMalloc((void**)&b.n_kept, 8));
+    HIPCHK(hipMemsetAsync(b.gate_ctl, 0, sizeof(StepCtl), stream));
+    HIPCHK(hipMemcpyAsync(b.gate_prog, gate->prog.ops.data(), gate->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
+  }
   for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
   StepCtl init;
   std::memset(&init, 0, sizeof(init));
@@ -88,18 +104,32 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
     if (head[0]) {
       const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)num_cus * 8));
       HIPCHK(hipEventRecord(b.ev[2], stream));
-      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, (const u64*)b.list,
-                         head[0], b.ctl, d_fps ? b.hits : nullptr, hit_cap, b.rows);
-      HIPCHK(hipGetLastError());
+      const u64* d_list = b.list;
+      if (gate) {                                                  // the constraint's verdicts, then the entries it permits (head[0] <= list_cap = the room of kept[])
+        HIPCHK(hipMemsetAsync(b.n_kept, 0, 8, stream));
+        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.gate_prog, (int)gate->prog.names.size(), d_words, d_refs, (const u64*)nullptr,
+                           (const u64*)b.list, head[0], b.gate_ctl, (u64*)nullptr, (u64)0, b.gate_rows);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_step_keep, dim3(grid_a), dim3(256), 0, stream, (const u64*)b.list, (const u32*)b.gate_rows, head[0], gate_k, b.kept, b.n_kept);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&head[0], b.n_kept, 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        d_list = b.kept;
+      }
+      if (head[0]) {
+        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, d_list,
+                           head[0], b.ctl, d_fps ? b.hits : nullptr, hit_cap, b.rows);
+        HIPCHK(hipGetLastError());
+      }
       HIPCHK(hipEventRecord(b.ev[3], stream));
       HIPCHK(hipStreamSynchronize(stream));
       HIPCHK(hipEventElapsedTime(&ms, b.ev[2], b.ev[3]));
       out->apply_ms += (double)ms;
-      if (want_rows) {
+      if (want_rows && head[0]) {
         const size_t at = out->row_entry.size();
         out->row_entry.resize(at + head[0]);
         out->row_val.resize(at + head[0]);
-        HIPCHK(hipMemcpy(out->row_entry.data() + at, b.list, head[0] * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->row_entry.data() + at, d_list, head[0] * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out->row_val.data() + at, b.rows, head[0] * 4, hipMemcpyDeviceToHost));
       }
     }
@@ -107,6 +137,11 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
   }
   HIPCHK(hipMemcpy(&out->h, b.ctl, sizeof(StepCtl), hipMemcpyDeviceToHost));
   out->h.scanned = scanned;
+  if (gate) {
+    StepCtl gh;
+    HIPCHK(hipMemcpy(&gh, b.gate_ctl, sizeof(StepCtl), hipMemcpyDeviceToHost));
+    out->h.n_internal += gh.n_internal;
+  }
   if (out->h.n_internal) return fail(VSRMC_E_HIP, "k_step_apply: " + std::to_string(out->h.n_internal) + " listed instances are not enabled (guard_slot_pre and gen disagree)");
   const u64 kept = d_fps ? std::min<u64>(out->h.n_hits, hit_cap) : 0;
   out->hits.resize(kept * 4);
@@ -236,9 +271,12 @@ int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_st
   const int bag = (c->bag_known && c->cur_max_bag) ? (int)std::min<u64>(c->cur_max_bag, (u64)M.max_bag) : M.max_bag;
   const u64 list_cap = std::min<u64>(STEP_LIST_CAP, std::max<u64>(64, c->n_frontier * (u64)ord_count(M, bag)));
   hit_cap = std::min<u64>(hit_cap, std::max<u64>(1, c->n_frontier * (u64)ord_count(M, M.max_bag)));   // (no level has more pairs than that)
+  // with an action constraint attached the scan is one of the constrained model: the transitions the constraint blocks are not judged, counted or listed
+  int gate_k = 0;
+  const vsrmc_where* gate = action_constraint_program(c, &gate_k);
   StepRun run;
   int rc = step_run(M, w, c->num_cus, c->stream, c->words[c->cur], c->off[c->cur], c->lvl_fp, 0, c->n_frontier, step_slice_default(M, bag, list_cap), list_cap,
-                    hit_cap, false, &run);
+                    hit_cap, false, &run, gate, gate_k);
   if (rc) return rc;
   const StepCtl& h = run.h;
   if (h.scanned != c->n_valid) return fail(VSRMC_E_HIP, "k_step_list: scanned " + std::to_string(h.scanned) + " records of " + std::to_string(c->n_valid));
@@ -277,7 +315,7 @@ int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_st
     if (out->min_index[p] == ~(u64)0) return fail(VSRMC_E_HIP, "step scan: the parent of a witness is not in the level");
     StepRun one;
     const u64 cap1 = (u64)std::max(64, ord_count(M, M.max_bag));
-    rc = step_run(M, w, c->num_cus, c->stream, c->words[c->cur], c->off[c->cur], nullptr, out->min_index[p], out->min_index[p] + 1, 1, cap1, 0, true, &one);
+    rc = step_run(M, w, c->num_cus, c->stream, c->words[c->cur], c->off[c->cur], nullptr, out->min_index[p], out->min_index[p] + 1, 1, cap1, 0, true, &one, gate, gate_k);
     if (rc) return rc;
     for (size_t k = 0; k < one.row_entry.size(); k++) {
       const u32 v = one.row_val[k];

@@ -651,6 +651,7 @@ extern "C" {
 int32_t vsrmc_checker_deepen(vsrmc_checker* c, vsrmc_level_info* inserted, vsrmc_level_info* probed) {
   if (!c || !inserted || !probed) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   int rc = deep_check_ready(c, 2, false);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->opt.device));
@@ -673,6 +674,7 @@ int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_lev
   if (!c || !virt || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2 starts from a materialised level");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   vsrmc_level_info none;
   int rc = vsrmc_checker_deepen(c, virt, probe);
@@ -686,6 +688,7 @@ int32_t vsrmc_checker_probe3(vsrmc_checker* c, vsrmc_level_info* virt1, vsrmc_le
   if (!c || !virt1 || !virt2 || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3 starts from a materialised level");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   std::memset(virt2, 0, sizeof(*virt2));
   virt2->viol_fp = virt2->viol_index = ~(u64)0;

@@ -27,6 +27,7 @@
 #include "vsr_constrain.hpp"
 #include "vsr_where_parse.hpp"
 #include "vsr_step.hpp"
+#include "vsr_action_constrain.hpp"
 #include "vsr_deep_where.hpp"
 #include "vsr_sim_where.hpp"
 
@@ -124,6 +125,7 @@ extern "C" {
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
 #include "host_constrain.hpp"    // state constraints: k_constrain over every level right after it is committed, per-level figures, the pruned list
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
+#include "host_action_constrain.hpp"   // action constraints: k_step_list / k_step_apply / k_step_expand in the place of k_expand, per-level figures, permitted traces
 #include "host_deep_where.hpp"   // state / step predicates on the levels beyond the record buffers: attachment, per-level results, witnesses; k_probe_where
 #include "host_sim_where.hpp"    // simulation with state / step predicates on every walk: k_simulate_where
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

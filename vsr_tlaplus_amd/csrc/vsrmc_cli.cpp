@@ -102,6 +102,12 @@ static void usage() {
       "                    are stored only: when the next one does not fit the record buffers the run ends, incomplete (exit 4).  -invariant NAMES are checked\n"
       "                    on the states the constraint prunes as well.  Not with -gpus N > 1, -simulate, -deepPredicates, -probeLast, -probe2At, -probe3At,\n"
       "                    -checkpoint, -recover, -audit.  With -json the level lines carry \"kept\" and \"pruned\"\n"
+      "  -actionConstraint NAME  with -steps FILE: the exported step predicate NAME is an action constraint (TLC's ACTION_CONSTRAINT): a transition that\n"
+      "                    fails it is generated and counted but not taken; its successor may still be reached through a permitted transition.  Init is not\n"
+      "                    subject to it; every behaviour printed takes permitted steps only.  Combines with -constraint, -invariant, -reach, -stepInvariant,\n"
+      "                    -stepReach, -checkDeadlock and -dumpTrace.  Levels are stored only, as with -constraint (exit 4 when the next one does not fit).\n"
+      "                    Not with -gpus N > 1, -simulate, -deepPredicates, -probeLast, -probe2At, -probe3At, -checkpoint, -recover, -audit.  With -json the\n"
+      "                    level lines carry \"permitted\" and \"blocked\"\n"
       "  -json             one JSON object per level on stdout instead of TLC-style progress lines\n");
 }
 
@@ -152,18 +158,20 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
-  bool deep_predicates = false, constrained = false;
+  bool deep_predicates = false, constrained = false, action_constrained = false;
   for (int i = 1; i < argc; i++) {
     if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
     if (std::string(argv[i]) == "-constraint") constrained = true;
+    if (std::string(argv[i]) == "-actionConstraint") action_constrained = true;
   }
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) {
       if (deep_predicates) { std::fprintf(stderr, "Error: -deepPredicates runs on one GPU: sharded checkers are not scanned (-gpus 1)\n"); return 2; }
       if (constrained) { std::fprintf(stderr, "Error: -constraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
+      if (action_constrained) { std::fprintf(stderr, "Error: -actionConstraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
       return exec_sharded(argc, argv, i);
     }
-  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, constraint_arg, steps_file, step_reach_arg, step_invariant_arg;
+  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, constraint_arg, action_constraint_arg, steps_file, step_reach_arg, step_invariant_arg;
   bool where_report = false, step_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
@@ -215,6 +223,7 @@ int main(int argc, char** argv) {
     else if (a == "-invariant" && i + 1 < argc) invariant_arg = argv[++i];
     else if (a == "-whereReport") where_report = true;
     else if (a == "-constraint" && i + 1 < argc) constraint_arg = argv[++i];
+    else if (a == "-actionConstraint" && i + 1 < argc) action_constraint_arg = argv[++i];
     else if (a == "-steps" && i + 1 < argc) steps_file = argv[++i];
     else if (a == "-stepReach" && i + 1 < argc) step_reach_arg = argv[++i];
     else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
@@ -233,6 +242,16 @@ int main(int argc, char** argv) {
                       : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-constraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
                       : (!chk_file.empty() || !recover_file.empty()) ? "-constraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
                       : audit ? "-constraint cannot be combined with -audit" : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
+  if (action_constrained) {                                       // refused before any device call
+    const char* why = action_constraint_arg.empty() ? "-actionConstraint needs a NAME"
+                      : steps_file.empty() ? "-actionConstraint NAME needs -steps FILE"
+                      : simulate ? "-actionConstraint belongs to the exhaustive search: a random walk (-simulate) is not constrained"
+                      : deep_predicates ? "-actionConstraint cannot be combined with -deepPredicates: the levels beyond the record buffers are not constrained"
+                      : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-actionConstraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
+                      : (!chk_file.empty() || !recover_file.empty()) ? "-actionConstraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
+                      : audit ? "-actionConstraint cannot be combined with -audit" : nullptr;
     if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
   }
   if (deep_predicates) {                                          // refused before any device call
@@ -354,6 +373,25 @@ int main(int argc, char** argv) {
       }
       if (vsrmc_step_predicates_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
+  }
+  // -actionConstraint NAME: a program of its own over the same file, every definition LOCAL and the constraint its one exported predicate
+  vsrmc_where* s_act = nullptr;
+  if (action_constrained) {
+    std::ifstream pf(steps_file, std::ios::binary);
+    if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", steps_file.c_str()); return 1; }
+    std::stringstream pss;
+    pss << pf.rdbuf();
+    const std::string text = pss.str();
+    vsrmc_where* whole = nullptr;
+    if (vsrmc_step_predicates_compile(m, text.c_str(), &whole) != 0) { std::fprintf(stderr, "Error: %s:%s\n", steps_file.c_str(), vsrmc_last_error()); return 1; }
+    vsrmc_where_desc wd;
+    vsrmc_where_describe(whole, &wd);
+    bool known = false;
+    for (int k = 0; k < wd.n_names; k++) known = known || action_constraint_arg == wd.names[k];
+    vsrmc_where_destroy(whole);
+    if (!known) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", steps_file.c_str(), action_constraint_arg.c_str()); return 2; }
+    const std::string local = make_local(text) + "\nActionConstraintQuery == " + action_constraint_arg;
+    if (vsrmc_step_predicates_compile(m, local.c_str(), &s_act) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
   }
   if (!reach_arg.empty() || !invariant_arg.empty() || where_report || constrained) {
     if (predicates_file.empty()) { std::fprintf(stderr, "Error: -reach / -invariant / -whereReport need -predicates FILE\n"); return 2; }
@@ -566,6 +604,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  if (s_act && vsrmc_checker_action_constrain_attach(c, s_act, 0) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   static const char* const MODULES[3] = {"VSR.tla", "VR_STATE_TRANSFER.tla", "VR_APP_STATE.tla"};
   std::printf("vsrmc: %s lowered: ReplicaCount=%d ClientCount=%d |Values|=%d StartViewOnTimerLimit=%d, %d permutation(s), "
               "invariant mask %d\n", MODULES[lay.module >= 0 && lay.module < 3 ? lay.module : 0], lay.replica_count, lay.client_count, lay.value_count, lay.start_view_on_timer_limit,
@@ -634,6 +676,19 @@ int main(int argc, char** argv) {
     return true;
   };
   con_collect();                                                  // (Init)
+  // -actionConstraint: the figures of every step taken under it, the run's totals
+  unsigned long long act_blocked_total = 0, act_blocked_by[16] = {0}, act_blocked_violating = 0;
+  int act_seen_level = 0;
+  vsrmc_action_constraint_info act_info;
+  std::memset(&act_info, 0, sizeof(act_info));
+  auto act_collect = [&]() -> bool {                              // true: a step not seen before (act_info holds it)
+    if (!s_act || vsrmc_checker_action_constraint_info(c, 0, &act_info) != 0 || act_info.level <= act_seen_level) return false;
+    act_seen_level = act_info.level;
+    act_blocked_total += (unsigned long long)act_info.blocked;
+    act_blocked_violating += (unsigned long long)act_info.blocked_violating;
+    for (int a2 = 0; a2 < 16; a2++) act_blocked_by[a2] += (unsigned long long)act_info.blocked_act[a2];
+    return true;
+  };
   unsigned long long cov[16] = {0};
   uint64_t viol_level = 0, viol_index = 0;
   int depth = info.level + info.reserved0;                        // (a recovered deep search: the levels beyond the stored one)
@@ -968,6 +1023,12 @@ int main(int argc, char** argv) {
     const bool con_new = con_collect();                           // the level this step stored and filtered (none: the step found no new state)
     if (json && w_con)
       where_json += ", \"kept\": " + std::to_string(con_new ? (unsigned long long)con_info.kept : 0ull) + ", \"pruned\": " + std::to_string(con_new ? (unsigned long long)con_info.pruned : 0ull);
+    const bool act_new = act_collect();                           // the step this call took under the action constraint
+    if (json && s_act)
+      where_json += ", \"permitted\": " + std::to_string(act_new ? (unsigned long long)act_info.permitted : 0ull) + ", \"blocked\": " + std::to_string(act_new ? (unsigned long long)act_info.blocked : 0ull);
+    if (!json && act_new)
+      std::printf("ActionConstraint(%d): %llu of %llu transitions were not taken, %llu taken, %llu new states.\n", act_info.level, (unsigned long long)act_info.blocked,
+                  (unsigned long long)act_info.pairs, (unsigned long long)act_info.permitted, (unsigned long long)act_info.n_new);
     if (json && scanned_this_step)                                // (terminal / unsettled: of the level this step expanded, like deadlocks)
       std::printf("{\"level\": %d, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"terminal\": %llu, \"unsettled\": %llu%s, \"seconds\": %.4f}\n",
                   info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -1137,6 +1198,13 @@ int main(int argc, char** argv) {
   }
   if (w_con && rc == 0)
     std::printf("CONSTRAINT %s: %llu states were out of model and not explored; the distinct states below are the in-model ones.\n", constraint_arg.c_str(), con_pruned_total);
+  if (s_act && rc == 0) {
+    std::string per;
+    for (int a2 = 0; a2 < 16; a2++)
+      if (act_blocked_by[a2]) per += std::string(per.empty() ? "" : ", ") + vsrmc_action_name(a2) + ": " + std::to_string(act_blocked_by[a2]);
+    std::printf("ACTION_CONSTRAINT %s: %llu transitions were not taken (per action: %s); %llu of their successors fail a built-in invariant (counted, not reported).\n",
+                action_constraint_arg.c_str(), act_blocked_total, per.empty() ? "none" : per.c_str(), act_blocked_violating);
+  }
   if (terminal_report && rc == 0) {
     unsigned long long n_term = 0, n_uns = 0;
     for (const TermRow& r : term_rows) { n_term += r.n_terminal; n_uns += r.n_unsettled; }
