@@ -1,13 +1,13 @@
 // host_action_constrain.hpp — action constraints: the host side of k_step_expand (vsr_action_constrain.hpp) — attaching one exported
 // predicate of a compiled step program to a checker, the level step that takes only the permitted transitions (phase_expand_gated, in the place of
-// phase_expand), the per-level figures, and the trace that takes only permitted steps (included by vsrmc.hip: one translation unit, the sections share
+// phase_expand: a consumer of step_slices, host_step_slices.hpp), the per-level figures, and the trace that takes only permitted steps (included by vsrmc.hip: one translation unit, the sections share
 // its anonymous-namespace helpers).
 #pragma once
 
 struct vsrmc_action_constraint {
   vsrmc_where prog;                    // a copy: the caller may destroy its own
   int k = 0;                           // the exported predicate that is the constraint
-  // device buffers, allocated once per attachment
+  DevMem mem;                          // device buffers, allocated once per attachment, freed with it
   u32* d_prog = nullptr;               // the program (uploaded once)
   u64* d_list = nullptr;               // the instance list of one slice (list_cap entries) ..
   u32* d_rows = nullptr;               // .. the verdict beside every entry ..
@@ -27,8 +27,6 @@ enum : u64 { ACTION_LIST_CAP = (u64)1 << 22 };
 void action_constraint_free(vsrmc_checker* c) {
   vsrmc_action_constraint* a = c->action_constraint;
   if (!a) return;
-  for (void* p : {(void*)a->d_prog, (void*)a->d_list, (void*)a->d_rows, (void*)a->d_live, (void*)a->d_sctl, (void*)a->d_actl})
-    if (p) (void)hipFree(p);
   for (hipEvent_t e : a->ev)
     if (e) (void)hipEventDestroy(e);
   delete a;
@@ -66,31 +64,25 @@ int phase_expand_gated(vsrmc_checker* c) {
   ActionCtl ah;
   std::memset(&ah, 0, sizeof(ah));
   ah.blocked_min_pfp = ah.blocked_viol_min_pfp = ~(u64)0;
-  StepCtl sh;
-  std::memset(&sh, 0, sizeof(sh));
-  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) sh.min_fp[k] = ~(u64)0;
+  StepCtl sh = fresh_ctl<StepCtl>();
   HIPCHK(hipMemcpyAsync(c->ctl, &c->h, sizeof(c->h), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(a->d_actl, &ah, sizeof(ah), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(a->d_sctl, &sh, sizeof(sh), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));                         // (the sources are pageable host memory on this frame)
-  auto* const list_kernel = M.model_id == 1 ? k_step_list<1> : M.model_id == 2 ? k_step_list<2> : k_step_list<0>;   // (where_fits at attach: the program is this model's)
-  auto* const apply_kernel = M.model_id == 1 ? k_step_apply<1> : M.model_id == 2 ? k_step_apply<2> : k_step_apply<0>;
-  auto* const expand_kernel = M.model_id == 1 ? k_step_expand<1> : M.model_id == 2 ? k_step_expand<2> : k_step_expand<0>;
+  auto* const apply_kernel = KERNEL_OF(k_step_apply, M);            // (where_fits at attach: the program is this model's)
+  auto* const expand_kernel = KERNEL_OF(k_step_expand, M);
   const int nxt = c->cur ^ 1;
-  const u64 n = c->n_frontier, list_cap = a->list_cap;
   const u64 nx_wcap = c->words_cap(nxt) > 256 ? c->words_cap(nxt) - 256 : 0;   // (a margin of one record: the writer copies the parent's words before it patches them)
   // the first slice cannot overflow the list even if every ordinal of every parent were enabled; the later ones are sized from the instances per parent the
   // slices before them showed (the largest mean of any slice of this level), times 1.5 — and a slice that overflows all the same is listed again in halves
-  // before anything of it is applied
+  // before anything of it is applied (SlicePolicy, adaptive).  TEST KNOB (documented in include/vsrmc.h): VSRMC_ACTION_SLICE, parents per slice, fixed (no
+  // adaptation: a halved slice grows back by doubling)
   const int bag = (c->bag_known && c->cur_max_bag) ? (int)std::min<u64>(c->cur_max_bag, (u64)M.max_bag) : M.max_bag;
-  u64 slice = std::max<u64>(1, list_cap / (u64)std::max(1, ord_count(M, bag)));
-  // TEST KNOB (documented in include/vsrmc.h): parents per slice, fixed (no adaptation)
   bool fixed_slice = false;
-  if (const char* e = std::getenv("VSRMC_ACTION_SLICE")) { slice = std::max<u64>(1, std::strtoull(e, nullptr, 10)); fixed_slice = true; }
-  slice = std::min<u64>(slice, a->live_cap);
-  const u64 slice0 = slice;
-  double ipp_max = 0, list_ms = 0, verdict_ms = 0, expand_ms = 0;
-  u64 scanned = 0, slices = 0, relisted = 0, launches = 0;
+  const u64 slice = slice_initial(a->list_cap, ord_count(M, bag), "VSRMC_ACTION_SLICE", &fixed_slice);
+  SlicePolicy sp(0, c->n_frontier, a->list_cap, slice, !fixed_slice, a->live_cap);
+  double list_ms = 0, verdict_ms = 0, expand_ms = 0;
+  u64 scanned = 0, launches = 0;
   bool timed = false;                                              // events 2..5 hold a slice whose kernel times have not been read yet
   auto collect = [&]() -> int {
     if (!timed) return 0;
@@ -102,61 +94,42 @@ int phase_expand_gated(vsrmc_checker* c) {
     timed = false;
     return 0;
   };
-  for (u64 pos = 0; pos < n;) {
-    const u64 end = std::min<u64>(n, pos + slice);
-    HIPCHK(hipMemsetAsync(a->d_sctl, 0, 16, c->stream));           // n_list, scanned: of this slice
-    HIPCHK(hipMemsetAsync(a->d_live, 0, (end - pos) * 4, c->stream));
-    const unsigned grid_l = (unsigned)std::max<u64>(1, std::min<u64>((end - pos + 255) / 256, (u64)c->num_cus * 8));
-    HIPCHK(hipEventRecord(a->ev[0], c->stream));
-    hipLaunchKernelGGL(list_kernel, dim3(grid_l), dim3(256), 0, c->stream, M, (const u64*)c->words[c->cur], (const u64*)c->off[c->cur], pos, end, a->d_list, list_cap, a->d_sctl);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(a->ev[1], c->stream));
-    u64 head[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(head, a->d_sctl, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int rc = collect();                                            // (the slice before this one has finished as well)
-    if (rc) return rc;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
-    list_ms += (double)ms;
-    slices++;
-    launches++;
-    if (head[0] > list_cap) {                                      // more instances than the list holds: the same parents again, half at a time, nothing of them applied
-      if (end - pos == 1) return fail(VSRMC_E_REP, "action constraint: one record has " + std::to_string(head[0]) + " enabled instances, the list holds " + std::to_string(list_cap));
-      slice = std::max<u64>(1, (end - pos) / 2);
-      relisted++;
-      continue;
-    }
-    scanned += head[1];
-    if (head[0]) {
-      const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)c->num_cus * 8));
-      HIPCHK(hipEventRecord(a->ev[2], c->stream));
-      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)a->d_prog, (int)a->prog.prog.names.size(), (const u64*)c->words[c->cur],
-                         (const u64*)c->off[c->cur], (const u64*)nullptr, (const u64*)a->d_list, head[0], a->d_sctl, (u64*)nullptr, (u64)0, a->d_rows);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(a->ev[3], c->stream));
-      HIPCHK(hipEventRecord(a->ev[4], c->stream));
-      hipLaunchKernelGGL(expand_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u64*)c->words[c->cur], (const u64*)c->off[c->cur], (const u64*)a->d_list,
-                         (const u32*)a->d_rows, head[0], a->k, c->level + 1, pos, c->table, c->tmask, c->words[nxt], nx_wcap, c->off[nxt], c->opt.frontier_states,
-                         c->lvl_fp, c->ctl, a->d_actl, a->d_live);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(a->ev[5], c->stream));
-      timed = true;
-      launches += 2;
-    }
-    if (fixed_slice) {
-      slice = std::min<u64>(slice0, slice * 2);                    // (a slice that was halved grows back once the dense region is behind)
-    } else {
-      ipp_max = std::max(ipp_max, (double)head[0] / (double)(end - pos));
-      slice = std::max<u64>(1, std::min<u64>(a->live_cap, (u64)((double)list_cap / (ipp_max * 1.5 + 1.0))));
-    }
-    pos = end;
-  }
+  // The only synchronisation of a slice is the one behind its listing: apply and expand of slice i run while the host sets up the listing of slice i + 1,
+  // and have finished when that listing has been waited for — their event times are read then (and once more after the loop).
+  const StepListing listing{c->words[c->cur], c->off[c->cur], c->stream, c->num_cus, a->d_list, a->d_sctl, a->ev[0], a->ev[1], &list_ms};
+  int rc = step_slices(
+      M, listing, sp, "action constraint", &scanned,
+      [&](u64 lo, u64 end) -> int {
+        HIPCHK(hipMemsetAsync(a->d_live, 0, (end - lo) * 4, c->stream));
+        return 0;
+      },
+      [&](u64 lo, u64, u64 n_inst) -> int {
+        const int rcc = collect();                                 // (the slice before this one has finished as well)
+        if (rcc) return rcc;
+        const unsigned grid_a = scan_grid(n_inst, c->num_cus);
+        HIPCHK(hipEventRecord(a->ev[2], c->stream));
+        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)a->d_prog, (int)a->prog.prog.names.size(), (const u64*)c->words[c->cur],
+                           (const u64*)c->off[c->cur], (const u64*)nullptr, (const u64*)a->d_list, n_inst, a->d_sctl, (u64*)nullptr, (u64)0, a->d_rows);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(a->ev[3], c->stream));
+        HIPCHK(hipEventRecord(a->ev[4], c->stream));
+        hipLaunchKernelGGL(expand_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u64*)c->words[c->cur], (const u64*)c->off[c->cur], (const u64*)a->d_list,
+                           (const u32*)a->d_rows, n_inst, a->k, c->level + 1, lo, c->table, c->tmask, c->words[nxt], nx_wcap, c->off[nxt], c->opt.frontier_states,
+                           c->lvl_fp, c->ctl, a->d_actl, a->d_live);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(a->ev[5], c->stream));
+        timed = true;
+        launches += 2;
+        return 0;
+      });
+  if (rc) return rc;
+  const u64 slices = sp.listings, relisted = sp.relisted;
+  launches += sp.listings;
   HIPCHK(hipMemcpyAsync(&c->h, c->ctl, sizeof(c->h), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(&ah, a->d_actl, sizeof(ah), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(&sh, a->d_sctl, sizeof(sh), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  int rc = collect();
+  rc = collect();
   if (rc) return rc;
   c->expand_ms = list_ms + verdict_ms + expand_ms;
   if (scanned != c->n_valid) { c->failed = 1; return fail(VSRMC_E_HIP, "k_step_list: scanned " + std::to_string(scanned) + " records of " + std::to_string(c->n_valid)); }
@@ -280,15 +253,14 @@ int32_t vsrmc_checker_action_constrain_attach(vsrmc_checker* c, const vsrmc_wher
   if (const char* e = std::getenv("VSRMC_ACTION_LIST_CAP")) a->list_cap = std::max<u64>(64, std::min<u64>(ACTION_LIST_CAP, std::strtoull(e, nullptr, 10)));
   a->live_cap = std::max<u64>(64, std::min<u64>(a->list_cap, c->opt.frontier_states));
   c->action_constraint = a;
-  hipError_t e = hipMalloc((void**)&a->d_prog, WHERE_MAX_OPS * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_list, a->list_cap * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_rows, a->list_cap * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_live, a->live_cap * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_sctl, sizeof(StepCtl));
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_actl, sizeof(ActionCtl));
+  (void)a->mem.upload(&a->d_prog, w->prog.ops.data(), w->prog.ops.size(), WHERE_MAX_OPS);
+  (void)a->mem.alloc(&a->d_list, a->list_cap * 8);
+  (void)a->mem.alloc(&a->d_rows, a->list_cap * 4);
+  (void)a->mem.alloc(&a->d_live, a->live_cap * 4);
+  (void)a->mem.alloc(&a->d_sctl, sizeof(StepCtl));
+  hipError_t e = a->mem.alloc(&a->d_actl, sizeof(ActionCtl));
   for (hipEvent_t& ev : a->ev)
     if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e == hipSuccess) e = hipMemcpy(a->d_prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     action_constraint_free(c);

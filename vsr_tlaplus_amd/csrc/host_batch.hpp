@@ -6,8 +6,8 @@
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-// upload n wire records as device-layout records with their H words filled in
-int upload_records(const Model& M, const u64* words, const u64* off, u64 n, u64** d_words, u64** d_off, u64* total_words) {
+// upload n wire records as device-layout records with their H words filled in (an offset array and hashing: not stage_batch's ref array); `mem` owns both
+int upload_records(const Model& M, const u64* words, const u64* off, u64 n, DevMem& mem, u64** d_words, u64** d_off, u64* total_words) {
   std::vector<u64> dev, doff(n + 1);
   dev.reserve((size_t)(off[n] + n * M.np));
   std::vector<u64> tmp(512);
@@ -22,11 +22,9 @@ int upload_records(const Model& M, const u64* words, const u64* off, u64 n, u64*
   }
   doff[n] = dev.size();
   *total_words = dev.size();
-  HIPCHK(hipMalloc((void**)d_words, std::max<size_t>(dev.size(), 1) * 8));
-  HIPCHK(hipMalloc((void**)d_off, (n + 1) * 8));
-  HIPCHK(hipMemcpy(*d_words, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(*d_off, doff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((M.model_id == 1 ? k_hash_records<1> : M.model_id == 2 ? k_hash_records<2> : k_hash_records<0>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, M, *d_words, *d_off, n);
+  HIPCHK(mem.upload(d_words, (const u64*)dev.data(), dev.size(), 1));
+  HIPCHK(mem.upload(d_off, (const u64*)doff.data(), doff.size()));
+  hipLaunchKernelGGL(KERNEL_OF(k_hash_records, M), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, M, *d_words, *d_off, n);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -45,15 +43,16 @@ int32_t vsrmc_expand_batch(const vsrmc_model* m, int32_t device, const uint64_t*
   *n_out = 0;
   *words_out = 0;
   if (n == 0) return 0;
+  DevMem mem;
   u64 *d_words = nullptr, *d_off = nullptr, *d_ow = nullptr, *d_om = nullptr, *d_cnt = nullptr, total = 0;
-  rc = upload_records(M, words, off, n, &d_words, &d_off, &total);
+  rc = upload_records(M, words, off, n, mem, &d_words, &d_off, &total);
   if (rc) return rc;
   u64 dev_words_cap = out_words_cap + out_cap * (u64)M.np;
-  HIPCHK(hipMalloc((void**)&d_ow, std::max<u64>(dev_words_cap, 1) * 8));
-  HIPCHK(hipMalloc((void**)&d_om, std::max<u64>(out_cap, 1) * 64));
-  HIPCHK(hipMalloc((void**)&d_cnt, 32));
+  HIPCHK(mem.alloc(&d_ow, std::max<u64>(dev_words_cap, 1) * 8));
+  HIPCHK(mem.alloc(&d_om, std::max<u64>(out_cap, 1) * 64));
+  HIPCHK(mem.alloc(&d_cnt, 32));
   HIPCHK(hipMemset(d_cnt, 0, 32));
-  hipLaunchKernelGGL((M.model_id == 1 ? k_successors<1> : M.model_id == 2 ? k_successors<2> : k_successors<0>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, M, d_words, d_off, n, d_ow, dev_words_cap,
+  hipLaunchKernelGGL(KERNEL_OF(k_successors, M), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, M, d_words, d_off, n, d_ow, dev_words_cap,
                      d_om, out_cap, d_cnt);
   HIPCHK(hipGetLastError());
   u64 cnt[4];
@@ -66,9 +65,7 @@ int32_t vsrmc_expand_batch(const vsrmc_model* m, int32_t device, const uint64_t*
     HIPCHK(hipMemcpy(hw.data(), d_ow, cnt[1] * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hm.data(), d_om, cnt[0] * 64, hipMemcpyDeviceToHost));
     // deterministic (parent, ordinal) order
-    std::vector<u64> order(cnt[0]);
-    for (u64 k = 0; k < cnt[0]; k++) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](u64 a, u64 b) {
+    const std::vector<u64> order = sorted_order(cnt[0], [&](u64 a, u64 b) {
       if (hm[8 * a] != hm[8 * b]) return hm[8 * a] < hm[8 * b];
       return hm[8 * a + 1] < hm[8 * b + 1];
     });
@@ -87,7 +84,6 @@ int32_t vsrmc_expand_batch(const vsrmc_model* m, int32_t device, const uint64_t*
     *n_out = cnt[0];
     *words_out = wpos;
   }
-  (void)hipFree(d_words); (void)hipFree(d_off); (void)hipFree(d_ow); (void)hipFree(d_om); (void)hipFree(d_cnt);
   return ret;
 }
 
@@ -179,8 +175,9 @@ int32_t vsrmc_fingerprint_batch(const vsrmc_model* m, int32_t device, const uint
   if (rc) return rc;
   if (n == 0) return 0;
   const Model& M = m->M;
+  DevMem mem;
   u64 *d_words = nullptr, *d_off = nullptr, total = 0;
-  rc = upload_records(M, words, off, n, &d_words, &d_off, &total);
+  rc = upload_records(M, words, off, n, mem, &d_words, &d_off, &total);
   if (rc) return rc;
   std::vector<u64> dev(total), doff(n + 1);
   HIPCHK(hipMemcpy(dev.data(), d_words, total * 8, hipMemcpyDeviceToHost));
@@ -192,7 +189,6 @@ int32_t vsrmc_fingerprint_batch(const vsrmc_model* m, int32_t device, const uint
     fps[i] = fp;
     if (auxkeys) auxkeys[i] = ak;
   }
-  (void)hipFree(d_words); (void)hipFree(d_off);
   return 0;
 }
 
@@ -217,12 +213,13 @@ extern "C" int32_t vsrmc_simulate(const vsrmc_model* m, int32_t device, uint32_t
   u32* d_depth = nullptr;
   u16* d_ords = nullptr;
   SimCtl* d_ctl = nullptr;
-  HIPCHK(hipMalloc((void**)&d_init, 512 * 8));
-  HIPCHK(hipMalloc((void**)&d_words, (u64)n_walkers * stride * 8));
-  HIPCHK(hipMalloc((void**)&d_rng, (u64)n_walkers * 8));
-  HIPCHK(hipMalloc((void**)&d_depth, (u64)n_walkers * 4));
-  HIPCHK(hipMalloc((void**)&d_ords, (u64)n_walkers * max_depth * 2));
-  HIPCHK(hipMalloc((void**)&d_ctl, sizeof(SimCtl)));
+  DevMem mem;
+  HIPCHK(mem.alloc(&d_init, 512 * 8));
+  HIPCHK(mem.alloc(&d_words, (u64)n_walkers * stride * 8));
+  HIPCHK(mem.alloc(&d_rng, (u64)n_walkers * 8));
+  HIPCHK(mem.alloc(&d_depth, (u64)n_walkers * 4));
+  HIPCHK(mem.alloc(&d_ords, (u64)n_walkers * max_depth * 2));
+  HIPCHK(mem.alloc(&d_ctl, sizeof(SimCtl)));
   HIPCHK(hipMemcpy(d_init, dev.data(), len * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(d_depth, 0xFF, (u64)n_walkers * 4));
   HIPCHK(hipMemset(d_ctl, 0, sizeof(SimCtl)));
@@ -266,7 +263,6 @@ extern "C" int32_t vsrmc_simulate(const vsrmc_model* m, int32_t device, uint32_t
     out->viol_steps = (int32_t)h.viol_depth;
     for (u32 k = 0; k < h.viol_depth && k < 512; k++) out->ords[k] = h.ords[k];
   }
-  (void)hipFree(d_init); (void)hipFree(d_words); (void)hipFree(d_rng); (void)hipFree(d_depth); (void)hipFree(d_ords); (void)hipFree(d_ctl);
   return 0;
 }
 

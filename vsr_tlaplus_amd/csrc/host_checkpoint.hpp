@@ -388,7 +388,7 @@ int32_t vsrmc_checker_select(vsrmc_checker* c, uint32_t action_mask, uint64_t ma
     (void)hipFree(d_idx);
     return fail(VSRMC_E_HIP, "hipMalloc failed");
   }
-  hipLaunchKernelGGL((M.model_id == 1 ? k_select<1> : M.model_id == 2 ? k_select<2> : k_select<0>), dim3((unsigned)((c->n_frontier + 255) / 256)), dim3(256), 0, c->stream, M, c->words[c->cur], c->off[c->cur],
+  hipLaunchKernelGGL(KERNEL_OF(k_select, M), dim3((unsigned)((c->n_frontier + 255) / 256)), dim3(256), 0, c->stream, M, c->words[c->cur], c->off[c->cur],
                      c->n_frontier, action_mask, d_idx, max_states, d_cnt);
   u64 cnt = 0;
   bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
@@ -455,7 +455,7 @@ static int32_t replay_path(const vsrmc_model* m, int32_t device, const uint32_t*
   HIPCHK(hipMemcpy(d_w, dev.data(), len * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(d_m, 0, (u64)std::max(nsteps, 1) * 32));
   if (nsteps > 0 && ords) HIPCHK(hipMemcpy(d_ords, ords, (u64)nsteps * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((M.model_id == 1 ? k_replay<1> : M.model_id == 2 ? k_replay<2> : k_replay<0>), dim3(1), dim3(64), 0, 0, M, d_w, d_o, d_ords, nsteps, d_m, d_fps,
+  hipLaunchKernelGGL(KERNEL_OF(k_replay, M), dim3(1), dim3(64), 0, 0, M, d_w, d_o, d_ords, nsteps, d_m, d_fps,
                      (u32*)nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());

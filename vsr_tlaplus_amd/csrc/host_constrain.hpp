@@ -6,7 +6,8 @@
 struct vsrmc_constraint {
   vsrmc_where prog;                    // a copy: the caller may destroy its own
   int k = 0;                           // the exported predicate that is the constraint
-  u32* d_prog = nullptr;               // device buffers, allocated once per attachment: the program (uploaded once) ..
+  DevMem mem;                          // owns the device buffers: allocated once per attachment, freed with it
+  u32* d_prog = nullptr;               // the program (uploaded once) ..
   ConstrainCtl* d_ctl = nullptr;       // .. the control block of one launch ..
   u64* d_list = nullptr;               // .. and the pruned fingerprints of one level
   u64 list_cap = 0;
@@ -35,9 +36,6 @@ bool constraint_reads_aux(const WhereProgram& p) {
 void constraint_free(vsrmc_checker* c) {
   vsrmc_constraint* a = c->constraint;
   if (!a) return;
-  if (a->d_prog) (void)hipFree(a->d_prog);
-  if (a->d_ctl) (void)hipFree(a->d_ctl);
-  if (a->d_list) (void)hipFree(a->d_list);
   delete a;
   c->constraint = nullptr;
 }
@@ -64,11 +62,10 @@ int constrain_level(vsrmc_checker* c, vsrmc_level_info* info) {
   // TEST KNOBS (documented in include/vsrmc.h): a shorter list, so that a test reaches the overflow path on a small space; fewer blocks, so that a small
   // level drives the grid-stride loop through several trips
   if (const char* e = std::getenv("VSRMC_WHERE_LIST_CAP")) cap = std::min<u64>(cap, std::max<u64>(1, std::strtoull(e, nullptr, 10)));
-  u64 grid64 = std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)c->num_cus * 8));
+  u64 grid64 = scan_grid(n, c->num_cus);
   if (const char* e = std::getenv("VSRMC_CONSTRAIN_GRID")) grid64 = std::max<u64>(1, std::min<u64>(grid64, std::strtoull(e, nullptr, 10)));
   HIPCHK(hipEventRecord(c->ev[2], c->stream));
-  auto* const kernel = M.model_id == 1 ? k_constrain<1> : M.model_id == 2 ? k_constrain<2> : k_constrain<0>;   // (where_fits at attach: the program is this model's)
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid64), dim3(256), 0, c->stream, M, (const u32*)a->d_prog, (int)a->prog.prog.names.size(), a->k,
+  hipLaunchKernelGGL(KERNEL_OF(k_constrain, M), dim3((unsigned)grid64), dim3(256), 0, c->stream, M, (const u32*)a->d_prog, (int)a->prog.prog.names.size(), a->k,
                      (const u64*)c->words[c->cur], c->off[c->cur], c->lvl_fp, n, a->d_ctl, a->d_list, cap);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[3], c->stream));
@@ -166,10 +163,9 @@ int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, i
   a->k = name_index;
   a->list_cap = std::max<u64>(1, std::min<u64>(c->opt.frontier_states, (u64)1 << 20));   // fingerprints kept per level; the counters and minima do not come from the list
   c->constraint = a;
-  hipError_t e = hipMalloc((void**)&a->d_prog, WHERE_MAX_OPS * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_ctl, sizeof(ConstrainCtl));
-  if (e == hipSuccess) e = hipMalloc((void**)&a->d_list, a->list_cap * 8);
-  if (e == hipSuccess) e = hipMemcpy(a->d_prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice);
+  (void)a->mem.upload(&a->d_prog, w->prog.ops.data(), w->prog.ops.size(), WHERE_MAX_OPS);
+  (void)a->mem.alloc(&a->d_ctl, sizeof(ConstrainCtl));
+  const hipError_t e = a->mem.alloc(&a->d_list, a->list_cap * 8);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     constraint_free(c);

@@ -1,12 +1,13 @@
 // host_deep_where.hpp — a user's predicates on the levels beyond the record buffers: the attachment of a state and / or a step program to a
-// checker, the three hooks a descent of the deep search calls (vsr_deep.hpp: deep_where_begin / _slice / _end), the per-level results and the witnesses
-// (included by vsrmc.hip after host_step.hpp: one translation unit, the sections share its anonymous-namespace helpers).
+// checker, the three hooks a descent of the deep search calls (vsr_deep.hpp: deep_where_begin / _slice / _end; _slice is a consumer of step_slices,
+// host_step_slices.hpp), the per-level results and the witnesses (included by vsrmc.hip after host_step.hpp: one translation unit, the sections share its
+// anonymous-namespace helpers).
 //
 // Every state of a seen-set-only level passes through a scratch buffer once per descent, as (words, off, fp, index range, holes included): the shape k_where
 // and k_step_list / k_step_apply take.  A level K beyond the base is scanned in the FIRST descent after the attachment that regenerates or inserts it
 // (scanned_through: the deepest level done), slice by slice; the figures of the slices of a level accumulate in one control block per level on the device,
-// reset once per level (the list cursors n_list / n_hits are per launch, as StepCtl::n_list is in step_run).  The successors of the inserted level's
-// sub-slices — the probed level, which has no records — go through k_probe_where (vsr_deep_where.hpp) from the instance list k_step_list wrote for k_step_apply.
+// reset once per level (the list cursors n_list / n_hits are per launch).  The successors of the inserted level's sub-slices — the probed level, which has
+// no records — go through k_probe_where (vsr_deep_where.hpp) from the instance list k_step_list wrote for k_step_apply.
 // Buffers are allocated once per attachment; the programs are uploaded once.
 #pragma once
 #include <map>
@@ -38,6 +39,7 @@ struct vsrmc_deep_attach {
   bool has_state = false, has_step = false;
   int scanned_through = 0;             // every level <= this one is either stored or has been scanned
   u64 where_cap = 0, hit_cap = 0, list_cap = 0;
+  DevMem mem;                          // the device buffers below: allocated once per attachment, freed with it
   u32 *d_prog_state = nullptr, *d_prog_step = nullptr;
   WhereCtl* d_wctl = nullptr;          // DEEP_MAX_LEVELS blocks: block i = level first + i of the descent in flight
   StepCtl* d_sctl = nullptr;
@@ -56,9 +58,6 @@ namespace {
 void deep_attach_free(vsrmc_checker* c) {
   vsrmc_deep_attach* A = c->deep_attach;
   if (!A) return;
-  for (void* p : {(void*)A->d_prog_state, (void*)A->d_prog_step, (void*)A->d_wctl, (void*)A->d_sctl, (void*)A->d_pctl, (void*)A->d_wlist, (void*)A->d_hits,
-                  (void*)A->d_list, (void*)A->d_plist})
-    if (p) (void)hipFree(p);
   delete A;
   c->deep_attach = nullptr;
 }
@@ -69,15 +68,6 @@ void deep_attach_restart(vsrmc_checker* c) {
   A->scanned_through = 1;              // (checker_seed: level 1 is the stored level)
   A->cur.clear();
   A->results.clear();
-}
-
-void deep_init_where_ctl(WhereCtl* h) {
-  std::memset(h, 0, sizeof(*h));
-  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) h->min_fp[k] = ~(u64)0;
-}
-void deep_init_step_ctl(StepCtl* h) {
-  std::memset(h, 0, sizeof(*h));
-  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) h->min_fp[k] = ~(u64)0;
 }
 
 // before a descent that regenerates / inserts the levels up to last_level: one control block per level that has not been scanned yet
@@ -91,9 +81,9 @@ int deep_where_begin(vsrmc_checker* c, int last_level) {
   const int n = last_level - A->first + 1;
   if (n > DEEP_MAX_LEVELS) return fail(VSRMC_E_REP, "deep predicates: more than 512 levels to scan in one descent");
   A->cur.resize((size_t)n);
-  std::vector<WhereCtl> w((size_t)n);
-  std::vector<StepCtl> s((size_t)n);
-  for (int i = 0; i < n; i++) { deep_init_where_ctl(&w[(size_t)i]); deep_init_step_ctl(&s[(size_t)i]); A->cur[(size_t)i].level = A->first + i; }
+  std::vector<WhereCtl> w((size_t)n, fresh_ctl<WhereCtl>());
+  std::vector<StepCtl> s((size_t)n, fresh_ctl<StepCtl>());
+  for (int i = 0; i < n; i++) A->cur[(size_t)i].level = A->first + i;
   HIPCHK(hipMemcpyAsync(A->d_wctl, w.data(), sizeof(WhereCtl) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(A->d_sctl, s.data(), sizeof(StepCtl) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(A->d_pctl, 0, sizeof(ProbeWhereCtl), c->stream));
@@ -116,10 +106,8 @@ int deep_where_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, in
     WhereCtl* ctl = A->d_wctl + idx;
     const u64 room = A->where_cap - L.where_raw.size() / 3;
     HIPCHK(hipMemsetAsync(&ctl->n_list, 0, 8, c->stream));         // the list cursor is this launch's; counters and minima go on from the slices before
-    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((part + 255) / 256, (u64)c->num_cus * 8));
-    auto* const kernel = M.model_id == 1 ? k_where<1> : M.model_id == 2 ? k_where<2> : k_where<0>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_state, (int)A->state.prog.names.size(), (const u64*)B.words, (const u64*)B.off,
-                       (const u64*)B.fp, part, (uint8_t*)nullptr, ctl, A->d_wlist, room);
+    hipLaunchKernelGGL(KERNEL_OF(k_where, M), dim3(scan_grid(part, c->num_cus)), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_state,
+                       (int)A->state.prog.names.size(), (const u64*)B.words, (const u64*)B.off, (const u64*)B.fp, part, (uint8_t*)nullptr, ctl, A->d_wlist, room);
     HIPCHK(hipGetLastError());
     u64 n_list = 0;
     HIPCHK(hipMemcpyAsync(&n_list, &ctl->n_list, 8, hipMemcpyDeviceToHost, c->stream));
@@ -136,66 +124,50 @@ int deep_where_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, in
   const bool probe = A->has_state && kind == DEEP_KIND_INSERTED && probe_next;
   if (A->has_state && kind == DEEP_KIND_INSERTED && !probe_next) A->probe_skipped = true;   // (a violating inserted level: nothing deeper is examined)
   if (!A->has_step && !probe) return 0;
-  // the transitions out of the slice: k_step_list over sub-slices of parents (step_run's loop over persistent buffers); the list feeds k_step_apply and,
-  // for the inserted level, k_probe_where
+  // the transitions out of the slice: sub-slices of parents through step_slices (host_step_slices.hpp) over the attachment's buffers; every list feeds
+  // k_step_apply and, for the inserted level, k_probe_where.  Host time, no events; the synchronisations behind k_step_apply and k_probe_where are this
+  // consumer's own (the hit cursor is read per launch; the next k_step_list rewrites the instance list).
   const double t1 = now_s();
   double probe_ms = 0;
   StepCtl* sctl = A->d_sctl + idx;
-  auto* const list_kernel = M.model_id == 1 ? k_step_list<1> : M.model_id == 2 ? k_step_list<2> : k_step_list<0>;
-  auto* const apply_kernel = M.model_id == 1 ? k_step_apply<1> : M.model_id == 2 ? k_step_apply<2> : k_step_apply<0>;
-  auto* const probe_kernel = M.model_id == 1 ? k_probe_where<1> : M.model_id == 2 ? k_probe_where<2> : k_probe_where<0>;
+  auto* const apply_kernel = KERNEL_OF(k_step_apply, M);
+  auto* const probe_kernel = KERNEL_OF(k_probe_where, M);
   const int bag_bound = bag ? (int)std::min<u64>(bag, (u64)M.max_bag) : M.max_bag;
-  const u64 slice0 = step_slice_default(M, bag_bound, A->list_cap);
-  u64 slice = slice0;
-  for (u64 pos = 0; pos < part;) {
-    const u64 end = std::min<u64>(part, pos + slice);
-    HIPCHK(hipMemsetAsync(sctl, 0, 16, c->stream));                // n_list, scanned: of this sub-slice
-    const unsigned grid_l = (unsigned)std::max<u64>(1, std::min<u64>((end - pos + 255) / 256, (u64)c->num_cus * 8));
-    hipLaunchKernelGGL(list_kernel, dim3(grid_l), dim3(256), 0, c->stream, M, (const u64*)B.words, (const u64*)B.off, pos, end, A->d_list, A->list_cap, sctl);
-    HIPCHK(hipGetLastError());
-    u64 head[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(head, sctl, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    L.step_launches++;
-    if (head[0] > A->list_cap) {                                   // more instances than the list holds: the same parents again, half at a time
-      if (end - pos == 1) return fail(VSRMC_E_REP, "deep predicates: one record has " + std::to_string(head[0]) + " enabled instances, the list holds " + std::to_string(A->list_cap));
-      slice = std::max<u64>(1, (end - pos) / 2);
-      continue;
-    }
-    L.step_scanned += head[1];
-    slice = std::min<u64>(slice0, slice * 2);
-    if (head[0]) {
-      const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)c->num_cus * 8));
-      if (A->has_step) {
-        const u64 room = A->hit_cap - L.step_raw.size() / 4;
-        HIPCHK(hipMemsetAsync(&sctl->n_hits, 0, 8, c->stream));
-        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_step, (int)A->step.prog.names.size(), (const u64*)B.words,
-                           (const u64*)B.off, (const u64*)B.fp, (const u64*)A->d_list, head[0], sctl, A->d_hits, room, (u32*)nullptr);
-        HIPCHK(hipGetLastError());
-        u64 n_hits = 0;
-        HIPCHK(hipMemcpyAsync(&n_hits, &sctl->n_hits, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        L.step_total += n_hits;
-        const u64 kept = std::min<u64>(n_hits, room);
-        if (kept) {
-          const size_t at = L.step_raw.size();
-          L.step_raw.resize(at + 4 * kept);
-          HIPCHK(hipMemcpy(L.step_raw.data() + at, A->d_hits, kept * 32, hipMemcpyDeviceToHost));
-        }
-      }
-      if (probe) {                                                 // the probed level: the cursor of its list runs through the whole pass
-        const double tp = now_s();
-        hipLaunchKernelGGL(probe_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_state, (const u64*)B.words, (const u64*)B.off,
-                           (const u64*)A->d_list, head[0], (const Slot*)c->table, c->tmask, level + 1, A->d_pctl, A->d_plist, A->where_cap);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));                   // (the next k_step_list rewrites the instance list)
-        A->probed.slices++;
-        A->probed.where_ms += (now_s() - tp) * 1e3;                // (k_probe_where's time is the probed level's, not the inserted level's step time)
-        probe_ms += (now_s() - tp) * 1e3;
+  SlicePolicy sp(0, part, A->list_cap, step_slice_default(M, bag_bound, A->list_cap));
+  const StepListing listing{B.words, B.off, c->stream, c->num_cus, A->d_list, sctl};
+  const int rc = step_slices(M, listing, sp, "deep predicates", &L.step_scanned, nullptr, [&](u64, u64, u64 n_inst) -> int {
+    const unsigned grid_a = scan_grid(n_inst, c->num_cus);
+    if (A->has_step) {
+      const u64 room = A->hit_cap - L.step_raw.size() / 4;
+      HIPCHK(hipMemsetAsync(&sctl->n_hits, 0, 8, c->stream));
+      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_step, (int)A->step.prog.names.size(), (const u64*)B.words,
+                         (const u64*)B.off, (const u64*)B.fp, (const u64*)A->d_list, n_inst, sctl, A->d_hits, room, (u32*)nullptr);
+      HIPCHK(hipGetLastError());
+      u64 n_hits = 0;
+      HIPCHK(hipMemcpyAsync(&n_hits, &sctl->n_hits, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      L.step_total += n_hits;
+      const u64 kept = std::min<u64>(n_hits, room);
+      if (kept) {
+        const size_t at = L.step_raw.size();
+        L.step_raw.resize(at + 4 * kept);
+        HIPCHK(hipMemcpy(L.step_raw.data() + at, A->d_hits, kept * 32, hipMemcpyDeviceToHost));
       }
     }
-    pos = end;
-  }
+    if (probe) {                                                   // the probed level: the cursor of its list runs through the whole pass
+      const double tp = now_s();
+      hipLaunchKernelGGL(probe_kernel, dim3(grid_a), dim3(256), 0, c->stream, M, (const u32*)A->d_prog_state, (const u64*)B.words, (const u64*)B.off,
+                         (const u64*)A->d_list, n_inst, (const Slot*)c->table, c->tmask, level + 1, A->d_pctl, A->d_plist, A->where_cap);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));                     // (the next k_step_list rewrites the instance list)
+      A->probed.slices++;
+      A->probed.where_ms += (now_s() - tp) * 1e3;                  // (k_probe_where's time is the probed level's, not the inserted level's step time)
+      probe_ms += (now_s() - tp) * 1e3;
+    }
+    return 0;
+  });
+  L.step_launches += sp.listings;
+  if (rc) return rc;
   L.step_ms += (now_s() - t1) * 1e3 - probe_ms;                    // k_step_list (also when it only feeds the probe) and k_step_apply
   return 0;
 }
@@ -211,14 +183,12 @@ int deep_where_resolve_probed(vsrmc_checker* c, int plevel) {
   P.kind = DEEP_KIND_PROBED;
   P.n_states = h.n_fresh;
   P.exact = h.n_list <= A->where_cap ? 1 : 0;
-  deep_init_where_ctl(&P.w);
+  P.w = fresh_ctl<WhereCtl>();
   P.w.scanned = h.n_fresh;
   const u64 kept = std::min<u64>(h.n_list, A->where_cap);
   std::vector<u64> raw(kept * 3);
   if (kept) HIPCHK(hipMemcpy(raw.data(), A->d_plist, kept * 24, hipMemcpyDeviceToHost));
-  std::vector<u64> order(kept);
-  for (u64 k = 0; k < kept; k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) {       // by fingerprint, then key: the first copy of a state carries its smallest key
+  const std::vector<u64> order = sorted_order(kept, [&](u64 a, u64 b) {       // by fingerprint, then key: the first copy of a state carries its smallest key
     if (raw[3 * a] != raw[3 * b]) return raw[3 * a] < raw[3 * b];
     if (raw[3 * a + 1] != raw[3 * b + 1]) return raw[3 * a + 1] < raw[3 * b + 1];
     return raw[3 * a + 2] < raw[3 * b + 2];
@@ -276,24 +246,20 @@ int deep_where_end(vsrmc_checker* c, int rc_in) {
       return fail(VSRMC_E_HIP, "deep predicates: level " + std::to_string(L.level) + " has " + std::to_string(c->deep_lv[(size_t)di].n_new) + " states, the scan saw " +
                                    std::to_string(L.n_states));
     const u64 kept = L.where_raw.size() / 3;
-    std::vector<u64> order(kept);
-    for (u64 k = 0; k < kept; k++) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](u64 a, u64 b) { return L.where_raw[3 * a] < L.where_raw[3 * b]; });
+    const std::vector<u64> order = sorted_order(kept, [&](u64 a, u64 b) { return L.where_raw[3 * a] < L.where_raw[3 * b]; });
     L.where_fps.resize(kept);
     L.where_bits.resize(kept);
     for (u64 k = 0; k < kept; k++) { L.where_fps[k] = L.where_raw[3 * order[k]]; L.where_bits[k] = (uint8_t)L.where_raw[3 * order[k] + 2]; }
     std::vector<u64>().swap(L.where_raw);
     const u64 hk = L.step_raw.size() / 4;
-    order.resize(hk);
-    for (u64 k = 0; k < hk; k++) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](u64 a, u64 b) {
+    const std::vector<u64> horder = sorted_order(hk, [&](u64 a, u64 b) {
       if (L.step_raw[4 * a] != L.step_raw[4 * b]) return L.step_raw[4 * a] < L.step_raw[4 * b];
       return L.step_raw[4 * a + 2] < L.step_raw[4 * b + 2];
     });
     L.step_fps.resize(hk);
     L.step_ords.resize(hk);
     L.step_bits.resize(hk);
-    for (u64 k = 0; k < hk; k++) { L.step_fps[k] = L.step_raw[4 * order[k]]; L.step_ords[k] = (uint32_t)L.step_raw[4 * order[k] + 2]; L.step_bits[k] = (uint8_t)L.step_raw[4 * order[k] + 3]; }
+    for (u64 k = 0; k < hk; k++) { L.step_fps[k] = L.step_raw[4 * horder[k]]; L.step_ords[k] = (uint32_t)L.step_raw[4 * horder[k] + 2]; L.step_bits[k] = (uint8_t)L.step_raw[4 * horder[k] + 3]; }
     std::vector<u64>().swap(L.step_raw);
     A->results[std::make_pair(L.level, 0)] = std::move(L);
   }
@@ -351,15 +317,21 @@ int32_t vsrmc_checker_deep_attach(vsrmc_checker* c, const vsrmc_where* state_pro
   if (const char* e = std::getenv("VSRMC_STEP_LIST_CAP")) A->hit_cap = std::min<u64>(A->hit_cap, std::max<u64>(1, std::strtoull(e, nullptr, 10)));
   // ... and a smaller INSTANCE list (at least 64 entries: one record's instances must fit), so that a sub-slice overflows it and is run again in halves
   if (const char* e = std::getenv("VSRMC_DEEP_INSTANCE_CAP")) A->list_cap = std::min<u64>(A->list_cap, std::max<u64>(64, std::strtoull(e, nullptr, 10)));
-  bool ok = hipMalloc((void**)&A->d_wctl, sizeof(WhereCtl) * DEEP_MAX_LEVELS) == hipSuccess && hipMalloc((void**)&A->d_sctl, sizeof(StepCtl) * DEEP_MAX_LEVELS) == hipSuccess &&
-            hipMalloc((void**)&A->d_pctl, sizeof(ProbeWhereCtl)) == hipSuccess && hipMalloc((void**)&A->d_list, A->list_cap * 8) == hipSuccess;
-  if (ok && A->has_state)
-    ok = hipMalloc((void**)&A->d_prog_state, WHERE_MAX_OPS * sizeof(u32)) == hipSuccess && hipMalloc((void**)&A->d_wlist, A->where_cap * 24) == hipSuccess &&
-         hipMalloc((void**)&A->d_plist, A->where_cap * 24) == hipSuccess &&
-         hipMemcpy(A->d_prog_state, A->state.prog.ops.data(), A->state.prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && A->has_step)
-    ok = hipMalloc((void**)&A->d_prog_step, WHERE_MAX_OPS * sizeof(u32)) == hipSuccess && hipMalloc((void**)&A->d_hits, A->hit_cap * 32) == hipSuccess &&
-         hipMemcpy(A->d_prog_step, A->step.prog.ops.data(), A->step.prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice) == hipSuccess;
+  DevMem& mem = A->mem;
+  (void)mem.alloc(&A->d_wctl, sizeof(WhereCtl) * DEEP_MAX_LEVELS);
+  (void)mem.alloc(&A->d_sctl, sizeof(StepCtl) * DEEP_MAX_LEVELS);
+  (void)mem.alloc(&A->d_pctl, sizeof(ProbeWhereCtl));
+  (void)mem.alloc(&A->d_list, A->list_cap * 8);
+  if (A->has_state) {
+    (void)mem.alloc(&A->d_wlist, A->where_cap * 24);
+    (void)mem.alloc(&A->d_plist, A->where_cap * 24);
+    (void)mem.upload(&A->d_prog_state, A->state.prog.ops.data(), A->state.prog.ops.size(), WHERE_MAX_OPS);
+  }
+  if (A->has_step) {
+    (void)mem.alloc(&A->d_hits, A->hit_cap * 32);
+    (void)mem.upload(&A->d_prog_step, A->step.prog.ops.data(), A->step.prog.ops.size(), WHERE_MAX_OPS);
+  }
+  const bool ok = mem.err == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     deep_attach_free(c);

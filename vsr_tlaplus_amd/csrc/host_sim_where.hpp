@@ -19,10 +19,7 @@ struct SimWhereBufs {
   u32 *depth = nullptr, *state_prog = nullptr, *step_prog = nullptr;
   u16* ords = nullptr;
   SimWhereCtl* ctl = nullptr;
-  ~SimWhereBufs() {
-    for (void* p : {(void*)init, (void*)words, (void*)rng, (void*)depth, (void*)state_prog, (void*)step_prog, (void*)ords, (void*)ctl})
-      if (p) (void)hipFree(p);
-  }
+  DevMem mem;
 };
 
 }  // namespace
@@ -51,14 +48,14 @@ extern "C" int32_t vsrmc_simulate_where(const vsrmc_model* m, int32_t device, co
   init_record_wire(M, wire);
   const int len = wire_to_device(M, wire.data(), dev.data());   // the H words stay 0: simulation never fingerprints
   SimWhereBufs b;
-  HIPCHK(hipMalloc((void**)&b.init, 512 * 8));
-  HIPCHK(hipMalloc((void**)&b.words, (u64)n_walkers * stride * 8));
-  HIPCHK(hipMalloc((void**)&b.rng, (u64)n_walkers * 8));
-  HIPCHK(hipMalloc((void**)&b.depth, (u64)n_walkers * 4));
-  HIPCHK(hipMalloc((void**)&b.ords, (u64)n_walkers * max_depth * 2));
-  HIPCHK(hipMalloc((void**)&b.ctl, sizeof(SimWhereCtl)));
-  HIPCHK(hipMalloc((void**)&b.state_prog, WHERE_MAX_OPS * sizeof(u32)));
-  HIPCHK(hipMalloc((void**)&b.step_prog, WHERE_MAX_OPS * sizeof(u32)));
+  HIPCHK(b.mem.alloc(&b.init, 512 * 8));
+  HIPCHK(b.mem.alloc(&b.words, (u64)n_walkers * stride * 8));
+  HIPCHK(b.mem.alloc(&b.rng, (u64)n_walkers * 8));
+  HIPCHK(b.mem.alloc(&b.depth, (u64)n_walkers * 4));
+  HIPCHK(b.mem.alloc(&b.ords, (u64)n_walkers * max_depth * 2));
+  HIPCHK(b.mem.alloc(&b.ctl, sizeof(SimWhereCtl)));
+  HIPCHK(b.mem.alloc(&b.state_prog, WHERE_MAX_OPS * sizeof(u32)));
+  HIPCHK(b.mem.alloc(&b.step_prog, WHERE_MAX_OPS * sizeof(u32)));
   HIPCHK(hipMemcpy(b.init, dev.data(), len * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(b.depth, 0xFF, (u64)n_walkers * 4));
   HIPCHK(hipMemset(b.ctl, 0, sizeof(SimWhereCtl)));

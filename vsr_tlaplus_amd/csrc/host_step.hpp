@@ -1,7 +1,7 @@
 // host_step.hpp — step predicates: the host side of k_step_list / k_step_apply (vsr_step.hpp) — compiling a text with primes (vsr_where_parse.hpp;
 // vsrmc_step_predicates_compile for any model, vsrmc_step_compile for VSR.tla alone), picking the model's instantiation, a
-// caller's batch, the scan of the checker's newest stored level over slices, the hit pairs the last scan left (included by vsrmc.hip: one translation
-// unit, the sections share its anonymous-namespace helpers).
+// caller's batch, the scan of the checker's newest stored level over slices (a consumer of step_slices, host_step_slices.hpp), the hit pairs the last
+// scan left (included by vsrmc.hip: one translation unit, the sections share its anonymous-namespace helpers).
 #pragma once
 
 namespace {
@@ -18,6 +18,7 @@ struct StepRun {
 };
 
 struct StepBufs {
+  DevMem mem;
   u64 *list = nullptr, *hits = nullptr;
   StepCtl* ctl = nullptr;
   u32 *prog = nullptr, *rows = nullptr;
@@ -27,23 +28,17 @@ struct StepBufs {
   u64 *kept = nullptr, *n_kept = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   ~StepBufs() {
-    for (void* p : {(void*)list, (void*)hits, (void*)ctl, (void*)prog, (void*)rows, (void*)gate_prog, (void*)gate_rows, (void*)gate_ctl, (void*)kept, (void*)n_kept})
-      if (p) (void)hipFree(p);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
 
-// parents per slice: the list cannot overflow when every ordinal of every parent of a slice is enabled (bag_bound = the largest bag a record can have)
-u64 step_slice_default(const Model& M, int bag_bound, u64 list_cap) {
-  u64 slice = std::max<u64>(1, list_cap / (u64)std::max(1, ord_count(M, bag_bound)));
-  // TEST KNOB (documented in include/vsrmc.h): parents per slice
-  if (const char* e = std::getenv("VSRMC_STEP_SLICE")) slice = std::max<u64>(1, std::strtoull(e, nullptr, 10));
-  return slice;
-}
+// parents per slice: the list cannot overflow when every ordinal of every parent of a slice is enabled (bag_bound = the largest bag a record can have);
+// TEST KNOB (documented in include/vsrmc.h): VSRMC_STEP_SLICE, parents per slice
+u64 step_slice_default(const Model& M, int bag_bound, u64 list_cap) { return slice_initial(list_cap, ord_count(M, bag_bound), "VSRMC_STEP_SLICE"); }
 
-// the records refs[lo, hi) through both kernels, slice by slice.  The device counter of the instance list is checked after every k_step_list: a slice
-// that offered more than the list holds is run again in two halves, nothing of it having been applied.
+// the records refs[lo, hi) through both kernels, slice by slice (step_slices, host_step_slices.hpp: a slice that offered more than the list holds is listed
+// again in two halves, nothing of it having been applied).
 // `gate` (a checker with an action constraint attached): exported predicate gate_k of that step program says which transitions the model
 // takes.  Every slice's list then goes through k_step_apply with the GATE's program first and through k_step_keep, and `w` runs over the permitted
 // instances only: counts, minima, hits and rows are those of the constrained model.  apply_ms then holds all three launches of a slice.
@@ -51,90 +46,66 @@ int step_run(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stre
              u64 slice, u64 list_cap, u64 hit_cap, bool want_rows, StepRun* out, const vsrmc_where* gate = nullptr, int gate_k = 0) {
   StepBufs b;
   hit_cap = d_fps ? std::max<u64>(1, hit_cap) : 1;
-  HIPCHK(hipMalloc((void**)&b.list, list_cap * 8));
-  HIPCHK(hipMalloc((void**)&b.hits, hit_cap * 32));
-  HIPCHK(hipMalloc((void**)&b.ctl, sizeof(StepCtl)));
-  HIPCHK(hipMalloc((void**)&b.prog, WHERE_MAX_OPS * sizeof(u32)));
-  if (want_rows) HIPCHK(hipMalloc((void**)&b.rows, list_cap * 4));
+  HIPCHK(b.mem.alloc(&b.list, list_cap * 8));
+  HIPCHK(b.mem.alloc(&b.hits, hit_cap * 32));
+  HIPCHK(b.mem.alloc(&b.ctl, sizeof(StepCtl)));
+  HIPCHK(b.mem.alloc(&b.prog, WHERE_MAX_OPS * sizeof(u32)));
+  if (want_rows) HIPCHK(b.mem.alloc(&b.rows, list_cap * 4));
   if (gate) {
-    HIPCHK(hipMalloc((void**)&b.gate_prog, WHERE_MAX_OPS * sizeof(u32)));
-    HIPCHK(hipMalloc((void**)&b.gate_rows, list_cap * 4));
-    HIPCHK(hipMalloc((void**)&b.gate_ctl, sizeof(StepCtl)));
-    HIPCHK(hipMalloc((void**)&b.kept, list_cap * 8));
-    HIPCHK(hipMalloc((void**)&b.n_kept, 8));
+    HIPCHK(b.mem.alloc(&b.gate_prog, WHERE_MAX_OPS * sizeof(u32)));
+    HIPCHK(b.mem.alloc(&b.gate_rows, list_cap * 4));
+    HIPCHK(b.mem.alloc(&b.gate_ctl, sizeof(StepCtl)));
+    HIPCHK(b.mem.alloc(&b.kept, list_cap * 8));
+    HIPCHK(b.mem.alloc(&b.n_kept, 8));
     HIPCHK(hipMemsetAsync(b.gate_ctl, 0, sizeof(StepCtl), stream));
     HIPCHK(hipMemcpyAsync(b.gate_prog, gate->prog.ops.data(), gate->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
   }
   for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
-  StepCtl init;
-  std::memset(&init, 0, sizeof(init));
-  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) init.min_fp[k] = ~(u64)0;
+  const StepCtl init = fresh_ctl<StepCtl>();
   HIPCHK(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(b.prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  // (where_fits: the program is this model's)
-  auto* const list_kernel = M.model_id == 1 ? k_step_list<1> : M.model_id == 2 ? k_step_list<2> : k_step_list<0>;
-  auto* const apply_kernel = M.model_id == 1 ? k_step_apply<1> : M.model_id == 2 ? k_step_apply<2> : k_step_apply<0>;
+  auto* const apply_kernel = KERNEL_OF(k_step_apply, M);            // (where_fits: the program is this model's)
   u64 scanned = 0;
-  slice = std::max<u64>(1, slice);
-  const u64 slice0 = slice;
-  for (u64 pos = lo; pos < hi;) {
-    const u64 end = std::min<u64>(hi, pos + slice);
-    HIPCHK(hipMemsetAsync(b.ctl, 0, 16, stream));                  // n_list, scanned: of this slice
-    const unsigned grid_l = (unsigned)std::max<u64>(1, std::min<u64>((end - pos + 255) / 256, (u64)num_cus * 8));
-    HIPCHK(hipEventRecord(b.ev[0], stream));
-    hipLaunchKernelGGL(list_kernel, dim3(grid_l), dim3(256), 0, stream, M, d_words, d_refs, pos, end, b.list, list_cap, b.ctl);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(b.ev[1], stream));
-    u64 head[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(head, b.ctl, 16, hipMemcpyDeviceToHost, stream));
+  SlicePolicy sp(lo, hi, list_cap, slice);
+  const StepListing listing{d_words, d_refs, stream, num_cus, b.list, b.ctl, b.ev[0], b.ev[1], &out->list_ms};
+  int rc = step_slices(M, listing, sp, "step scan", &scanned, nullptr, [&](u64, u64, u64 n_inst) -> int {
+    const unsigned grid_a = scan_grid(n_inst, num_cus);
+    HIPCHK(hipEventRecord(b.ev[2], stream));
+    const u64* d_list = b.list;
+    if (gate) {                                                    // the constraint's verdicts, then the entries it permits (n_inst <= list_cap = the room of kept[])
+      HIPCHK(hipMemsetAsync(b.n_kept, 0, 8, stream));
+      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.gate_prog, (int)gate->prog.names.size(), d_words, d_refs, (const u64*)nullptr,
+                         (const u64*)b.list, n_inst, b.gate_ctl, (u64*)nullptr, (u64)0, b.gate_rows);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(k_step_keep, dim3(grid_a), dim3(256), 0, stream, (const u64*)b.list, (const u32*)b.gate_rows, n_inst, gate_k, b.kept, b.n_kept);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(&n_inst, b.n_kept, 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      d_list = b.kept;
+    }
+    if (n_inst) {
+      hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, d_list, n_inst,
+                         b.ctl, d_fps ? b.hits : nullptr, hit_cap, b.rows);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(b.ev[3], stream));
     HIPCHK(hipStreamSynchronize(stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
-    out->list_ms += (double)ms;
-    out->slices++;
-    if (head[0] > list_cap) {                                      // more instances than the list holds: the same parents again, half at a time
-      if (end - pos == 1) return fail(VSRMC_E_REP, "step scan: one record has " + std::to_string(head[0]) + " enabled instances, the list holds " + std::to_string(list_cap));
-      slice = std::max<u64>(1, (end - pos) / 2);
-      out->retried++;
-      continue;
+    HIPCHK(hipEventElapsedTime(&ms, b.ev[2], b.ev[3]));
+    out->apply_ms += (double)ms;
+    if (want_rows && n_inst) {
+      const size_t at = out->row_entry.size();
+      out->row_entry.resize(at + n_inst);
+      out->row_val.resize(at + n_inst);
+      HIPCHK(hipMemcpy(out->row_entry.data() + at, d_list, n_inst * 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(out->row_val.data() + at, b.rows, n_inst * 4, hipMemcpyDeviceToHost));
     }
-    scanned += head[1];
-    slice = std::min<u64>(slice0, slice * 2);                      // (a slice that was halved grows back once the dense region is behind)
-    if (head[0]) {
-      const unsigned grid_a = (unsigned)std::max<u64>(1, std::min<u64>((head[0] + 255) / 256, (u64)num_cus * 8));
-      HIPCHK(hipEventRecord(b.ev[2], stream));
-      const u64* d_list = b.list;
-      if (gate) {                                                  // the constraint's verdicts, then the entries it permits (head[0] <= list_cap = the room of kept[])
-        HIPCHK(hipMemsetAsync(b.n_kept, 0, 8, stream));
-        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.gate_prog, (int)gate->prog.names.size(), d_words, d_refs, (const u64*)nullptr,
-                           (const u64*)b.list, head[0], b.gate_ctl, (u64*)nullptr, (u64)0, b.gate_rows);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_step_keep, dim3(grid_a), dim3(256), 0, stream, (const u64*)b.list, (const u32*)b.gate_rows, head[0], gate_k, b.kept, b.n_kept);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&head[0], b.n_kept, 8, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        d_list = b.kept;
-      }
-      if (head[0]) {
-        hipLaunchKernelGGL(apply_kernel, dim3(grid_a), dim3(256), 0, stream, M, (const u32*)b.prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, d_list,
-                           head[0], b.ctl, d_fps ? b.hits : nullptr, hit_cap, b.rows);
-        HIPCHK(hipGetLastError());
-      }
-      HIPCHK(hipEventRecord(b.ev[3], stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      HIPCHK(hipEventElapsedTime(&ms, b.ev[2], b.ev[3]));
-      out->apply_ms += (double)ms;
-      if (want_rows && head[0]) {
-        const size_t at = out->row_entry.size();
-        out->row_entry.resize(at + head[0]);
-        out->row_val.resize(at + head[0]);
-        HIPCHK(hipMemcpy(out->row_entry.data() + at, d_list, head[0] * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->row_val.data() + at, b.rows, head[0] * 4, hipMemcpyDeviceToHost));
-      }
-    }
-    pos = end;
-  }
+    return 0;
+  });
+  out->slices += sp.listings;
+  out->retried += sp.relisted;
+  if (rc) return rc;
   HIPCHK(hipMemcpy(&out->h, b.ctl, sizeof(StepCtl), hipMemcpyDeviceToHost));
   out->h.scanned = scanned;
   if (gate) {
@@ -157,33 +128,14 @@ int32_t vsrmc_step_compile(const vsrmc_model* m, const char* text, vsrmc_where**
   if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
   *out = nullptr;
   if (m->M.model_id != 0) return fail(VSRMC_E_ARG, "step predicates: VSR.tla only");
-  vsrmc_where* w = new vsrmc_where();
-  std::string err;
-  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err, true);
-  if (rc) {
-    delete w;
-    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
-  }
-  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry;
-  *out = w;
-  return 0;
+  return compile_predicates(m, text, true, out);
 }
 
 // the model-generic entry: VSR.tla -> what vsrmc_step_compile gives, op for op; the analysis models -> the step language over their own variable table
 int32_t vsrmc_step_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out) {
   if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
   if (m->M.model_id == 0) return vsrmc_step_compile(m, text, out);
-  *out = nullptr;
-  vsrmc_where* w = new vsrmc_where();
-  std::string err;
-  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err, true);
-  if (rc) {
-    delete w;
-    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
-  }
-  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry; w->model_id = m->M.model_id;
-  *out = w;
-  return 0;
+  return compile_predicates(m, text, true, out);
 }
 
 int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where* w, const uint64_t* words, const uint64_t* off, uint64_t n, uint64_t* rows,
@@ -196,27 +148,13 @@ int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where
   if (rc) return rc;
   if (n == 0) return 0;
   const Model& M = m->M;
-  std::vector<u64> dev, refs(n), tmp(512);
-  dev.reserve((size_t)(off[n] + n * (u64)(M.fixed - M.h0)));
+  DevMem mem;
+  u64 *d_words = nullptr, *d_refs = nullptr;
   int bag = 0;
-  for (u64 i = 0; i < n; i++) {
-    const u64* r = words + off[i];
-    const int nmsg = hdr_nmsg(r[0]);
-    if ((u64)(M.h0 + nmsg) != off[i + 1] - off[i]) return fail(VSRMC_E_ARG, "record length does not match its header");
-    if (nmsg > M.max_bag) return fail(VSRMC_E_REP, "record bag larger than max_bag");
-    bag = std::max(bag, nmsg);
-    const int len = wire_to_device(M, r, tmp.data());
-    refs[i] = ((u64)dev.size() << 8) | (u64)len;
-    dev.insert(dev.end(), tmp.begin(), tmp.begin() + len);
-  }
+  rc = stage_batch(M, words, off, n, beyond_max_bag, mem, &d_words, &d_refs, &bag);
+  if (rc) return rc;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
-  u64 *d_words = nullptr, *d_refs = nullptr;
-  struct Free { void** p[2]; ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); } } guard{{(void**)&d_words, (void**)&d_refs}};
-  HIPCHK(hipMalloc((void**)&d_words, dev.size() * 8));
-  HIPCHK(hipMalloc((void**)&d_refs, n * 8));
-  HIPCHK(hipMemcpy(d_words, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_refs, refs.data(), n * 8, hipMemcpyHostToDevice));
   const u64 list_cap = std::min<u64>(STEP_LIST_CAP, std::max<u64>(64, n * (u64)ord_count(M, bag)));
   StepRun run;
   rc = step_run(M, w, prop.multiProcessorCount, nullptr, d_words, d_refs, nullptr, 0, n, step_slice_default(M, bag, list_cap), list_cap, 0, true, &run);
@@ -226,9 +164,7 @@ int32_t vsrmc_step_batch(const vsrmc_model* m, int32_t device, const vsrmc_where
   *n_rows = total;
   if (!rows) return 0;                                            // size query
   if (cap_rows < total) return fail(VSRMC_E_ARG, "row buffer too small");
-  std::vector<u64> order(total);
-  for (u64 k = 0; k < total; k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) {        // (parent, ordinal): the order of vsrmc_expand_batch
+  const std::vector<u64> order = sorted_order(total, [&](u64 a, u64 b) {        // (parent, ordinal): the order of vsrmc_expand_batch
     const u64 ea = run.row_entry[a], eb = run.row_entry[b];
     if (origin_pidx(ea) != origin_pidx(eb)) return origin_pidx(ea) < origin_pidx(eb);
     return origin_ord(ea) < origin_ord(eb);
@@ -289,9 +225,7 @@ int32_t vsrmc_checker_step_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_st
   out->slices = run.slices;
   for (int k = 0; k < WHERE_MAX_EXPORTS; k++) { out->count[k] = h.count[k]; out->min_fp[k] = h.min_fp[k]; }
   const u64 kept = run.hits.size() / 4;
-  std::vector<u64> order(kept);
-  for (u64 k = 0; k < kept; k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) {
+  const std::vector<u64> order = sorted_order(kept, [&](u64 a, u64 b) {
     if (run.hits[4 * a] != run.hits[4 * b]) return run.hits[4 * a] < run.hits[4 * b];
     return run.hits[4 * a + 2] < run.hits[4 * b + 2];
   });

@@ -5,8 +5,6 @@
 
 namespace {
 
-typedef void (*TerminalKernel)(Model, const u64*, const u64*, const u64*, u64, uint8_t*, TermCtl*, u64*, u64);
-
 // one launch over n refs; the TermCtl at d_ctl is initialised here
 int launch_terminal(const Model& M, int num_cus, hipStream_t stream, const u64* d_words, const u64* d_refs, const u64* d_fps, u64 n, uint8_t* d_flags,
                     TermCtl* d_ctl, u64* d_list, u64 list_cap) {
@@ -14,9 +12,7 @@ int launch_terminal(const Model& M, int num_cus, hipStream_t stream, const u64* 
   std::memset(&init, 0, sizeof(init));
   init.min_fp = init.min_fp_unsettled = ~(u64)0;
   HIPCHK(hipMemcpyAsync(d_ctl, &init, sizeof(init), hipMemcpyHostToDevice, stream));
-  const TerminalKernel kernel = M.model_id == 1 ? k_terminal<1> : M.model_id == 2 ? k_terminal<2> : k_terminal<0>;
-  const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)num_cus * 8));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, M, d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list, list_cap);
+  hipLaunchKernelGGL(KERNEL_OF(k_terminal, M), dim3(scan_grid(n, num_cus)), dim3(256), 0, stream, M, d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list, list_cap);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -31,30 +27,16 @@ int32_t vsrmc_terminal_batch(const vsrmc_model* m, int32_t device, const uint64_
   if (rc) return rc;
   if (n == 0) return 0;
   const Model& M = m->M;
-  // device-layout records (the H words stay 0: guards never read them) behind a ref array, as a level has it
-  std::vector<u64> dev, refs(n), tmp(512);
-  dev.reserve((size_t)(off[n] + n * (u64)(M.fixed - M.h0)));
-  for (u64 i = 0; i < n; i++) {
-    const u64* w = words + off[i];
-    const int nmsg = hdr_nmsg(w[0]);
-    if ((u64)(M.h0 + nmsg) != off[i + 1] - off[i]) return fail(VSRMC_E_ARG, "record length does not match its header");
-    if (M.fixed + nmsg > 255) return fail(VSRMC_E_REP, "record longer than 255 words");
-    const int len = wire_to_device(M, w, tmp.data());
-    refs[i] = ((u64)dev.size() << 8) | (u64)len;
-    dev.insert(dev.end(), tmp.begin(), tmp.begin() + len);
-  }
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
+  DevMem mem;
   u64 *d_words = nullptr, *d_refs = nullptr;
   uint8_t* d_flags = nullptr;
   TermCtl* d_ctl = nullptr;
-  struct Free { void** p[4]; ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); } } guard{{(void**)&d_words, (void**)&d_refs, (void**)&d_flags, (void**)&d_ctl}};
-  HIPCHK(hipMalloc((void**)&d_words, dev.size() * 8));
-  HIPCHK(hipMalloc((void**)&d_refs, n * 8));
-  HIPCHK(hipMalloc((void**)&d_flags, n));
-  HIPCHK(hipMalloc((void**)&d_ctl, sizeof(TermCtl)));
-  HIPCHK(hipMemcpy(d_words, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_refs, refs.data(), n * 8, hipMemcpyHostToDevice));
+  rc = stage_batch(M, words, off, n, longer_than_255, mem, &d_words, &d_refs);
+  if (rc) return rc;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, device));
+  HIPCHK(mem.alloc(&d_flags, n));
+  HIPCHK(mem.alloc(&d_ctl, sizeof(TermCtl)));
   HIPCHK(hipMemset(d_flags, 0, n));
   rc = launch_terminal(M, prop.multiProcessorCount, nullptr, d_words, d_refs, nullptr, n, d_flags, d_ctl, nullptr, 0);
   if (rc) return rc;
@@ -85,11 +67,11 @@ int32_t vsrmc_checker_terminal_scan(vsrmc_checker* c, vsrmc_terminal_info* out) 
   u64 cap = std::min<u64>(c->n_frontier, (u64)1 << 20);          // list entries kept (24 B each); the counters and minima do not come from the list
   // TEST KNOB (documented in include/vsrmc.h): a smaller list, so that a test can reach the overflow path on a small space
   if (const char* e = std::getenv("VSRMC_TERMINAL_LIST_CAP")) cap = std::min<u64>(cap, std::max<u64>(1, std::strtoull(e, nullptr, 10)));
+  DevMem mem;
   u64* d_list = nullptr;
   TermCtl* d_ctl = nullptr;
-  struct Free { void** p[2]; ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); } } guard{{(void**)&d_list, (void**)&d_ctl}};
-  HIPCHK(hipMalloc((void**)&d_list, cap * 24));
-  HIPCHK(hipMalloc((void**)&d_ctl, sizeof(TermCtl)));
+  HIPCHK(mem.alloc(&d_list, cap * 24));
+  HIPCHK(mem.alloc(&d_ctl, sizeof(TermCtl)));
   HIPCHK(hipEventRecord(c->ev[0], c->stream));
   int rc = launch_terminal(M, c->num_cus, c->stream, c->words[c->cur], c->off[c->cur], c->lvl_fp, c->n_frontier, nullptr, d_ctl, d_list, cap);
   if (rc) return rc;
@@ -109,9 +91,7 @@ int32_t vsrmc_checker_terminal_scan(vsrmc_checker* c, vsrmc_terminal_info* out) 
   const u64 kept = std::min<u64>(h.n_list, cap);
   std::vector<u64> raw(kept * 3);
   if (kept) HIPCHK(hipMemcpy(raw.data(), d_list, kept * 24, hipMemcpyDeviceToHost));
-  std::vector<u64> order(kept);
-  for (u64 k = 0; k < kept; k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) { return raw[3 * a] < raw[3 * b]; });
+  const std::vector<u64> order = sorted_order(kept, [&](u64 a, u64 b) { return raw[3 * a] < raw[3 * b]; });
   c->term_fps.resize(kept);
   c->term_flags.resize(kept);
   for (u64 k = 0; k < kept; k++) {

@@ -17,15 +17,15 @@ int32_t vsrmc_tlc_fingerprint_batch(const vsrmc_model* m, int32_t device, const 
   if (n == 0) return 0;
   for (u64 i = 0; i < n; i++)
     if (hdr_nmsg(words[off[i]]) > vsr::tlcfp::MAX_MSGS) return fail(VSRMC_E_REP, "record bag larger than the TLC fingerprint mode orders");
+  DevMem mem;
   u64 *d_words = nullptr, *d_off = nullptr, *d_out = nullptr, total = 0;
-  rc = upload_records(M, words, off, n, &d_words, &d_off, &total);
+  rc = upload_records(M, words, off, n, mem, &d_words, &d_off, &total);
   if (rc) return rc;
-  bool ok = hipMalloc((void**)&d_out, n * 8) == hipSuccess;
+  bool ok = mem.alloc(&d_out, n * 8) == hipSuccess;
   if (ok) {
     hipLaunchKernelGGL(vsr::tlcfp::k_tlc_fingerprints, dim3((unsigned)std::min<u64>((n + 255) / 256, 4096)), dim3(256), 0, 0, M, d_words, d_off, (const u64*)nullptr, n, d_out);
     ok = hipGetLastError() == hipSuccess && hipMemcpy(fps, d_out, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d_words); (void)hipFree(d_off); (void)hipFree(d_out);
   return ok ? 0 : fail(VSRMC_E_HIP, "k_tlc_fingerprints failed");
 }
 

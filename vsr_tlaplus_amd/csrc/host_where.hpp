@@ -1,14 +1,8 @@
 // host_where.hpp — state predicates: the host side of k_where (vsr_where.hpp) — compiling a text (vsr_where_parse.hpp; vsrmc_predicates_compile for any model,
-// vsrmc_where_compile for VSR.tla alone), picking the model's instantiation, a caller's batch, the scan of
+// vsrmc_where_compile for VSR.tla alone; both through compile_predicates, host_scan_common.hpp, where vsrmc_where lives), a caller's batch, the scan of
 // the checker's newest stored level, the list the last scan left (included by vsrmc.hip: one translation unit, the sections share its
 // anonymous-namespace helpers).
 #pragma once
-
-struct vsrmc_where {
-  WhereProgram prog;
-  int R, C, n, L, symmetry;            // the model it was compiled for: the unfolding depends on these
-  int model_id = 0;                    // and the layout the loads address (vsrmc_predicates_compile; the two older entries compile for VSR.tla only)
-};
 
 namespace {
 
@@ -20,16 +14,12 @@ bool where_fits(const vsrmc_where* w, const Model& M, int symmetry) {
 // are recorded around the kernel alone
 int launch_where(const Model& M, const vsrmc_where* w, int num_cus, hipStream_t stream, u32* d_prog, const u64* d_words, const u64* d_refs, const u64* d_fps, u64 n,
                  uint8_t* d_flags, WhereCtl* d_ctl, u64* d_list, u64 list_cap, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-  WhereCtl init;
-  std::memset(&init, 0, sizeof(init));
-  for (int k = 0; k < WHERE_MAX_EXPORTS; k++) init.min_fp[k] = ~(u64)0;
+  const WhereCtl init = fresh_ctl<WhereCtl>();
   HIPCHK(hipMemcpyAsync(d_ctl, &init, sizeof(init), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_prog, w->prog.ops.data(), w->prog.ops.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
   HIPCHK(hipStreamSynchronize(stream));                            // (both sources are pageable host memory that the caller may free)
-  const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)num_cus * 8));
   if (e0) HIPCHK(hipEventRecord(e0, stream));
-  auto* const kernel = M.model_id == 1 ? k_where<1> : M.model_id == 2 ? k_where<2> : k_where<0>;   // (where_fits: the program is this model's)
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, M, (const u32*)d_prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list,
+  hipLaunchKernelGGL(KERNEL_OF(k_where, M), dim3(scan_grid(n, num_cus)), dim3(256), 0, stream, M, (const u32*)d_prog, (int)w->prog.names.size(), d_words, d_refs, d_fps, n, d_flags, d_ctl, d_list,
                      list_cap);
   HIPCHK(hipGetLastError());
   if (e1) HIPCHK(hipEventRecord(e1, stream));
@@ -44,33 +34,14 @@ int32_t vsrmc_where_compile(const vsrmc_model* m, const char* text, vsrmc_where*
   if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
   *out = nullptr;
   if (m->M.model_id != 0) return fail(VSRMC_E_ARG, "state predicates: VSR.tla only");
-  vsrmc_where* w = new vsrmc_where();
-  std::string err;
-  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err);
-  if (rc) {
-    delete w;
-    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
-  }
-  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry;
-  *out = w;
-  return 0;
+  return compile_predicates(m, text, false, out);
 }
 
 // the model-generic entry: VSR.tla -> what vsrmc_where_compile gives, op for op; the analysis models -> their own variable table (vsr_where_parse.hpp)
 int32_t vsrmc_predicates_compile(const vsrmc_model* m, const char* text, vsrmc_where** out) {
   if (!m || !text || !out) return fail(VSRMC_E_ARG, "NULL argument");
   if (m->M.model_id == 0) return vsrmc_where_compile(m, text, out);
-  *out = nullptr;
-  vsrmc_where* w = new vsrmc_where();
-  std::string err;
-  const int rc = where_compile(m->M, m->symmetry != 0, m->value_names, text, &w->prog, &err);
-  if (rc) {
-    delete w;
-    return fail(rc == 2 ? VSRMC_E_REP : VSRMC_E_ARG, err);
-  }
-  w->R = m->M.R; w->C = m->M.C; w->n = m->M.n; w->L = m->M.L; w->symmetry = m->symmetry; w->model_id = m->M.model_id;
-  *out = w;
-  return 0;
+  return compile_predicates(m, text, false, out);
 }
 
 void vsrmc_where_destroy(vsrmc_where* w) { delete w; }
@@ -96,31 +67,18 @@ int32_t vsrmc_where_batch(const vsrmc_model* m, int32_t device, const vsrmc_wher
   if (rc) return rc;
   if (n == 0) return 0;
   const Model& M = m->M;
-  std::vector<u64> dev, refs(n), tmp(512);
-  dev.reserve((size_t)(off[n] + n * (u64)(M.fixed - M.h0)));
-  for (u64 i = 0; i < n; i++) {
-    const u64* r = words + off[i];
-    const int nmsg = hdr_nmsg(r[0]);
-    if ((u64)(M.h0 + nmsg) != off[i + 1] - off[i]) return fail(VSRMC_E_ARG, "record length does not match its header");
-    if (M.fixed + nmsg > 255) return fail(VSRMC_E_REP, "record longer than 255 words");
-    const int len = wire_to_device(M, r, tmp.data());
-    refs[i] = ((u64)dev.size() << 8) | (u64)len;
-    dev.insert(dev.end(), tmp.begin(), tmp.begin() + len);
-  }
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
+  DevMem mem;
   u64 *d_words = nullptr, *d_refs = nullptr;
   uint8_t* d_flags = nullptr;
   WhereCtl* d_ctl = nullptr;
   u32* d_prog = nullptr;
-  struct Free { void** p[5]; ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); } } guard{{(void**)&d_words, (void**)&d_refs, (void**)&d_flags, (void**)&d_ctl, (void**)&d_prog}};
-  HIPCHK(hipMalloc((void**)&d_words, dev.size() * 8));
-  HIPCHK(hipMalloc((void**)&d_refs, n * 8));
-  HIPCHK(hipMalloc((void**)&d_flags, n));
-  HIPCHK(hipMalloc((void**)&d_ctl, sizeof(WhereCtl)));
-  HIPCHK(hipMalloc((void**)&d_prog, WHERE_MAX_OPS * sizeof(u32)));
-  HIPCHK(hipMemcpy(d_words, dev.data(), dev.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_refs, refs.data(), n * 8, hipMemcpyHostToDevice));
+  rc = stage_batch(M, words, off, n, longer_than_255, mem, &d_words, &d_refs);
+  if (rc) return rc;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, device));
+  HIPCHK(mem.alloc(&d_flags, n));
+  HIPCHK(mem.alloc(&d_ctl, sizeof(WhereCtl)));
+  HIPCHK(mem.alloc(&d_prog, WHERE_MAX_OPS * sizeof(u32)));
   HIPCHK(hipMemset(d_flags, 0, n));
   rc = launch_where(M, w, prop.multiProcessorCount, nullptr, d_prog, d_words, d_refs, nullptr, n, d_flags, d_ctl, nullptr, 0);
   if (rc) return rc;
@@ -153,13 +111,13 @@ int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_w
   u64 cap = std::min<u64>(c->n_frontier, (u64)1 << 20);          // list entries kept (24 B each); the counters and minima do not come from the list
   // TEST KNOB (documented in include/vsrmc.h): a smaller list, so that a test can reach the overflow path on a small space
   if (const char* e = std::getenv("VSRMC_WHERE_LIST_CAP")) cap = std::min<u64>(cap, std::max<u64>(1, std::strtoull(e, nullptr, 10)));
+  DevMem mem;
   u64* d_list = nullptr;
   WhereCtl* d_ctl = nullptr;
   u32* d_prog = nullptr;
-  struct Free { void** p[3]; ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); } } guard{{(void**)&d_list, (void**)&d_ctl, (void**)&d_prog}};
-  HIPCHK(hipMalloc((void**)&d_list, cap * 24));
-  HIPCHK(hipMalloc((void**)&d_ctl, sizeof(WhereCtl)));
-  HIPCHK(hipMalloc((void**)&d_prog, WHERE_MAX_OPS * sizeof(u32)));
+  HIPCHK(mem.alloc(&d_list, cap * 24));
+  HIPCHK(mem.alloc(&d_ctl, sizeof(WhereCtl)));
+  HIPCHK(mem.alloc(&d_prog, WHERE_MAX_OPS * sizeof(u32)));
   int rc = launch_where(M, w, c->num_cus, c->stream, d_prog, c->words[c->cur], c->off[c->cur], c->lvl_fp, c->n_frontier, nullptr, d_ctl, d_list, cap, c->ev[0], c->ev[1]);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -174,9 +132,7 @@ int32_t vsrmc_checker_where_scan(vsrmc_checker* c, const vsrmc_where* w, vsrmc_w
   const u64 kept = std::min<u64>(h.n_list, cap);
   std::vector<u64> raw(kept * 3);
   if (kept) HIPCHK(hipMemcpy(raw.data(), d_list, kept * 24, hipMemcpyDeviceToHost));
-  std::vector<u64> order(kept);
-  for (u64 k = 0; k < kept; k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) { return raw[3 * a] < raw[3 * b]; });
+  const std::vector<u64> order = sorted_order(kept, [&](u64 a, u64 b) { return raw[3 * a] < raw[3 * b]; });
   c->where_fps.resize(kept);
   c->where_bits.resize(kept);
   for (u64 k = 0; k < kept; k++) {

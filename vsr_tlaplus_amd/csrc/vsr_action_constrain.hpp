@@ -38,22 +38,6 @@ struct ActionCtl {
   u64 live_parents;                   // parents with at least one listed instance
 };
 
-__device__ __forceinline__ u32 actc_wave_sum32(u32 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (u32)__shfl_xor((int)v, d);
-  return v;
-}
-__device__ __forceinline__ u32 actc_wave_max32(u32 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, (u32)__shfl_xor((int)v, d));
-  return v;
-}
-__device__ __forceinline__ u32 actc_wave_or32(u32 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v |= (u32)__shfl_xor((int)v, d);
-  return v;
-}
-
 // add one per lane of `who` to s_cnt[action]: one LDS atomic per distinct action of the wave, issued by the first lane that has it
 __device__ __forceinline__ void actc_count_actions(unsigned long long* s_cnt, bool who, int action, int lane) {
   u64 rem = __ballot(who);
@@ -199,8 +183,8 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
     }
   }
   // the end of the launch: every lane of the wave is here (the loop above only `continue`s at wave-uniform points); one reduction and one atomic per counter and wave
-  const u32 w_probes = actc_wave_sum32(probes), w_ties = actc_wave_sum32(n_ties), w_bag = actc_wave_max32(bag), w_vmask = actc_wave_or32(vmask), w_bmask = actc_wave_or32(bmask);
-  const u64 w_vmin = term_wave_min(vmin), w_bmin = term_wave_min(bmin), w_bvmin = term_wave_min(bvmin);
+  const u32 w_probes = wave_sum32(probes), w_ties = wave_sum32(n_ties), w_bag = wave_max32(bag), w_vmask = wave_or32(vmask), w_bmask = wave_or32(bmask);
+  const u64 w_vmin = wave_min64(vmin), w_bmin = wave_min64(bmin), w_bvmin = wave_min64(bvmin);
   if (lane == 0) {
     if (n_gen) atomicAdd((unsigned long long*)&ctl->generated, (unsigned long long)n_gen);
     if (n_written) atomicAdd((unsigned long long*)&ctl->n_written, (unsigned long long)n_written);

@@ -29,25 +29,6 @@ struct ConstrainCtl {
   u64 n_list;                         // pruned states offered to the list
 };
 
-__device__ __forceinline__ u64 constrain_wave_sum(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (u64)__shfl_xor((unsigned long long)v, d);
-  return v;
-}
-__device__ __forceinline__ u64 constrain_wave_xor(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v ^= (u64)__shfl_xor((unsigned long long)v, d);
-  return v;
-}
-__device__ __forceinline__ u64 constrain_wave_max(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const u64 o = (u64)__shfl_xor((unsigned long long)v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 template <int MODEL>
 __global__ void __launch_bounds__(256)
 k_constrain(Model M, const u32* __restrict__ prog, int n_exports, int k_bit, const u64* __restrict__ words, u64* refs, u64* fps, u64 n, ConstrainCtl* ctl,
@@ -67,6 +48,8 @@ k_constrain(Model M, const u32* __restrict__ prog, int n_exports, int k_bit, con
     const bool valid = ref != 0;
     const u64* rec = words + (ref >> 8);
     const int nmsg = valid ? hdr_nmsg(rec[0]) : 0;
+    // (wave_max_uniform written out: through the helper this kernel compiles to one v_xor fewer, and the change that introduced the helper left every
+    // kernel's code as it was)
     int wmax = nmsg;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
@@ -93,9 +76,9 @@ k_constrain(Model M, const u32* __restrict__ prog, int n_exports, int k_bit, con
     if (pos < list_cap) list[pos] = fp;
   }
   // the end of the launch: every lane of the wave is here (the loop above only `continue`s), one reduction and one atomic per counter and wave
-  const u64 w_kept = constrain_wave_sum(kept), w_pruned = constrain_wave_sum(pruned);
+  const u64 w_kept = wave_sum64(kept), w_pruned = wave_sum64(pruned);
   if (w_kept) {
-    const u64 w_words = constrain_wave_sum(kwords), w_bag = constrain_wave_max(bag), w_xor = constrain_wave_xor(kxor), w_sum = constrain_wave_sum(ksum);
+    const u64 w_words = wave_sum64(kwords), w_bag = wave_max64(bag), w_xor = wave_xor64(kxor), w_sum = wave_sum64(ksum);
     if (lane_id() == 0) {
       atomicAdd((unsigned long long*)&ctl->kept, (unsigned long long)w_kept);
       atomicAdd((unsigned long long*)&ctl->kept_words, (unsigned long long)w_words);
@@ -105,7 +88,7 @@ k_constrain(Model M, const u32* __restrict__ prog, int n_exports, int k_bit, con
     }
   }
   if (w_pruned) {                                                  // (wave-uniform)
-    const u64 w_min = term_wave_min(pmin);
+    const u64 w_min = wave_min64(pmin);
     if (lane_id() == 0) {
       atomicAdd((unsigned long long*)&ctl->pruned, (unsigned long long)w_pruned);
       atomicMin((unsigned long long*)&ctl->pruned_min_fp, (unsigned long long)w_min);
@@ -113,9 +96,9 @@ k_constrain(Model M, const u32* __restrict__ prog, int n_exports, int k_bit, con
 #pragma unroll
     for (int p = 0; p < WHERE_MAX_EXPORTS; p++) {
       if (p >= n_exports) break;
-      const u64 w_c = constrain_wave_sum(pcnt[p]);
+      const u64 w_c = wave_sum64(pcnt[p]);
       if (w_c == 0) continue;
-      const u64 w_m = term_wave_min(pminf[p]);
+      const u64 w_m = wave_min64(pminf[p]);
       if (lane_id() == 0) {
         atomicAdd((unsigned long long*)&ctl->p_count[p], (unsigned long long)w_c);
         atomicMin((unsigned long long*)&ctl->p_min_fp[p], (unsigned long long)w_m);

@@ -247,6 +247,31 @@ __device__ __forceinline__ u64 wave_alloc(u64* counter) {
   return base + (u64)__popcll(active & (((u64)1 << lane) - 1));
 }
 
+// Butterfly reductions over the 64 lanes of a wave: every lane ends with the result, and all 64 must call together.  One name per operation and width
+// (XCHG: the type __shfl_xor moves it as; OP combines the lane's value v with the partner's o).
+#define VSR_WAVE_REDUCE(NAME, T, XCHG, OP)                  \
+  __device__ __forceinline__ T NAME(T v) {                  \
+    _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) {   \
+      const T o = (T)__shfl_xor((XCHG)v, d);                \
+      v = OP;                                               \
+    }                                                       \
+    return v;                                               \
+  }
+VSR_WAVE_REDUCE(wave_min64, u64, unsigned long long, o < v ? o : v)
+VSR_WAVE_REDUCE(wave_max64, u64, unsigned long long, o > v ? o : v)
+VSR_WAVE_REDUCE(wave_sum64, u64, unsigned long long, v + o)
+VSR_WAVE_REDUCE(wave_xor64, u64, unsigned long long, v ^ o)
+VSR_WAVE_REDUCE(wave_sum32, u32, int, v + o)
+VSR_WAVE_REDUCE(wave_max32, u32, int, max(v, o))
+VSR_WAVE_REDUCE(wave_or32, u32, int, v | o)
+#undef VSR_WAVE_REDUCE
+// the wave's largest value in a scalar register: the trip count of a loop the whole wave walks together (the longest bag of its records)
+__device__ __forceinline__ int wave_max_uniform(int v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
 // Find-or-insert of a fingerprint: linear probing from fp & mask, one 64-byte line (4 slots) per memory round trip.  The home slot (16 B)
 // is read first, the rest of its line only when that slot holds another fingerprint.
 // A loaded line may be stale with respect to concurrent inserts, which is harmless: a slot only ever goes empty -> fp and

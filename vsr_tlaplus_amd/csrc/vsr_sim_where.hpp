@@ -52,12 +52,6 @@ struct SimWhereStack {                // [slot][lane of the block]
   __device__ __forceinline__ int& operator[](int slot) const { return base[slot * SIMW_BLOCK]; }
 };
 
-__device__ __forceinline__ int simw_wave_max(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-  return (int)VSR_WHERE_UNI(v);
-}
-
 // cnt[k] += lanes with bit k; reached by the whole wave
 __device__ __forceinline__ void simw_count(u32 bits, int n_exports, u32* cnt) {
   if (__ballot(bits != 0) == 0) return;                            // (wave-uniform)
@@ -139,7 +133,7 @@ k_simulate_where(Model Marg, const u64* __restrict__ init_rec, int init_len, u64
     u32 sbits = 0;
     if constexpr (HAS_STEP) {
       const int nmsg_p = step ? hdr_nmsg(w[0]) : 0, nmsg_c = step ? hdr_nmsg(D.hdr) : 0;
-      const int wmax = simw_wave_max(max(nmsg_p, nmsg_c));
+      const int wmax = wave_max_uniform(max(nmsg_p, nmsg_c));
       const StepPair<MODEL> pair{(const u64*)w, D, M.fixed, 1 + ((int)D.r - 1) * M.wpr, M.wpr, nmsg_p, nmsg_c, (int)D.action};
       const u32 raw = where_run<SimWhereStack, const u64*, StepPair<MODEL>, MODEL>(step_prog, M.fixed, (const u64*)w, step, nmsg_p, wmax, S, pair);
       sbits = step ? raw : 0;                                      // (a lane without a pair ran the program over zeros: TRUE would count it)
@@ -177,7 +171,7 @@ k_simulate_where(Model Marg, const u64* __restrict__ init_rec, int init_len, u64
     u32 wbits = 0;
     if constexpr (HAS_STATE) {
       const int nmsg = stands ? hdr_nmsg(w[0]) : 0;
-      const int wmax = simw_wave_max(nmsg);
+      const int wmax = wave_max_uniform(nmsg);
       const u32 raw = where_run<SimWhereStack, const u64*, WhereNoPair, MODEL>(state_prog, M.fixed, (const u64*)w, stands, nmsg, wmax, S);
       wbits = stands ? raw : 0;                                    // (a lane without a state ran the program over zeros: TRUE would count it)
       n_states += (u32)__popcll(__ballot(stands));

@@ -91,10 +91,7 @@ k_step_list(Model M, const u64* __restrict__ words, const u64* __restrict__ refs
         if (r <= M.R) Areg[r] = rec[1 + (r - 1) * M.wpr];
     }
     const int nslots = valid ? M.m0 + hdr_nmsg(hdr) : 0;
-    int wslots = nslots;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wslots = max(wslots, __shfl_xor(wslots, d));
-    wslots = (int)VSR_WHERE_UNI(wslots);
+    const int wslots = wave_max_uniform(nslots);
     for (int slot = 0; slot < wslots; slot++) {
       int kind0 = 0;
       u32 mask = slot < nslots ? ModelOps<MODEL>::guard_pre(M, rec, hdr, Areg, slot, &kind0, -1) : 0u;
@@ -137,6 +134,8 @@ k_step_apply(Model M, const u32* __restrict__ prog, int n_exports, const u64* __
     const bool err = have && enabled && D.err != 0;
     const bool valid = have && enabled && D.err == 0;
     const int nmsg_p = valid ? hdr_nmsg(rec[0]) : 0, nmsg_c = valid ? hdr_nmsg(D.hdr) : 0;
+    // (wave_max_uniform written out: through the helper this kernel compiles to one v_xor fewer, and the change that introduced the helper left every
+    // kernel's code as it was)
     int wmax = max(nmsg_p, nmsg_c);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
@@ -158,7 +157,7 @@ k_step_apply(Model M, const u32* __restrict__ prog, int n_exports, const u64* __
       if (b == 0) continue;
       cnt[k] += (u32)__popcll(b);
       if (fps) {
-        const u64 m = term_wave_min(hit ? fp : ~(u64)0);
+        const u64 m = wave_min64(hit ? fp : ~(u64)0);
         if (lane_id() == 0) atomicMin((unsigned long long*)&ctl->min_fp[k], (unsigned long long)m);
       }
     }

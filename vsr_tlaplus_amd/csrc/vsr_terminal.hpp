@@ -44,15 +44,6 @@ VSR_HD int term_unsettled(const Model& M, PTR rec) {
   return bad;
 }
 
-__device__ __forceinline__ u64 term_wave_min(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const u64 o = (u64)__shfl_xor((unsigned long long)v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
 // what every lane does with its record's verdict (valid = the lane has a record); all 64 lanes of the wave call it together
 __device__ __forceinline__ void term_emit(bool valid, bool terminal, int unsettled, u64 i, const u64* __restrict__ fps, uint8_t* flags, TermCtl* ctl,
                                           u64* list, u64 list_cap, u64& n_scanned, u64& n_term, u64& n_uns) {
@@ -65,8 +56,8 @@ __device__ __forceinline__ void term_emit(bool valid, bool terminal, int unsettl
   if (!fps) return;
   if (__ballot(t) == 0) return;                                  // (wave-uniform)
   const u64 fp = t ? fps[i] : ~(u64)0;
-  const u64 m = term_wave_min(fp);
-  const u64 mu = term_wave_min((t && unsettled) ? fp : ~(u64)0);
+  const u64 m = wave_min64(fp);
+  const u64 mu = wave_min64((t && unsettled) ? fp : ~(u64)0);
   if (lane_id() == 0) {
     atomicMin((unsigned long long*)&ctl->min_fp, (unsigned long long)m);
     if (mu != ~(u64)0) atomicMin((unsigned long long*)&ctl->min_fp_unsettled, (unsigned long long)mu);

@@ -246,10 +246,7 @@ k_where(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restr
     const bool valid = ref != 0;
     const u64* rec = words + (ref >> 8);
     const int nmsg = valid ? hdr_nmsg(rec[0]) : 0;
-    int wmax = nmsg;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d));
-    wmax = (int)VSR_WHERE_UNI(wmax);
+    const int wmax = wave_max_uniform(nmsg);
     const u32 raw = where_run<WhereLdsStack, const u64*, WhereNoPair, MODEL>(prog, M.fixed, rec, valid, nmsg, wmax, S);
     const u32 bits = valid ? raw : 0;                              // (a lane without a record ran the program over zeros: TRUE would count it)
     if (valid && flags) flags[i] = (uint8_t)bits;
@@ -263,7 +260,7 @@ k_where(Model M, const u32* __restrict__ prog, int n_exports, const u64* __restr
       if (b == 0) continue;
       cnt[k] += (u32)__popcll(b);
       if (fps) {
-        const u64 m = term_wave_min(hit ? fps[i] : ~(u64)0);
+        const u64 m = wave_min64(hit ? fps[i] : ~(u64)0);
         if (lane_id() == 0) atomicMin((unsigned long long*)&ctl->min_fp[k], (unsigned long long)m);
       }
     }

@@ -109,6 +109,7 @@ const char* const VRAS_TLA_SHA256 = "6ef22989c86c9d5bb9c9c9829a09e9ee0e035c75e7b
 // ---- the sections of the host side, one file per concern (one translation unit: they share the helpers above) ------------------
 #include "host_model.hpp"        // models, cfg reader, state printing / parsing
 #include "host_fpset.hpp"        // FPSet / StateQueue handles
+#include "host_scan_common.hpp"  // shared by the batches and the predicate scans: KERNEL_OF, scan_grid, fresh_ctl, DevMem, stage_batch, compile_predicates
 #include "host_batch.hpp"        // expand / fingerprint batches, trace import, simulation
 #include "host_checker.hpp"      // the checker: buffers, level phases, passes, trace walks
 extern "C" {
@@ -124,6 +125,7 @@ extern "C" {
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
 #include "host_constrain.hpp"    // state constraints: k_constrain over every level right after it is committed, per-level figures, the pruned list
+#include "host_step_slices.hpp"  // the slice driver of k_step_list (step_slices) over the slice policy (host_slice_policy.hpp)
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
 #include "host_action_constrain.hpp"   // action constraints: k_step_list / k_step_apply / k_step_expand in the place of k_expand, per-level figures, permitted traces
 #include "host_deep_where.hpp"   // state / step predicates on the levels beyond the record buffers: attachment, per-level results, witnesses; k_probe_where
