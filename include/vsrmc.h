@@ -710,6 +710,58 @@ int32_t vsrmc_simulate_where(const vsrmc_model* m, int32_t device, const vsrmc_w
                              int32_t stop, uint32_t n_walkers, int32_t max_depth, uint64_t seed,
                              double max_seconds, uint64_t max_rounds, vsrmc_sim_where_result* out);
 
+/* ---- simulation mode under a state constraint and / or an action constraint (csrc/vsr_sim_constrain.hpp: k_simulate_constrained) -----
+ * [TLC-RECALLED] TLC's simulator honours CONSTRAINT and ACTION_CONSTRAINT: a walk moves only along permitted transitions into in-model states.  The
+ * constrained BFS (vsrmc_checker_constrain_attach, vsrmc_checker_action_constrain_attach) ends with the stored levels; walks go to any depth.
+ * vsrmc_simulate and vsrmc_simulate_where are unchanged.
+ * state_prog (vsrmc_predicates_compile, may be NULL): its export state_constraint (an index, or -1 for none) is the state constraint, every other
+ *   export is a query as in vsrmc_simulate_where.  step_prog (vsrmc_step_predicates_compile, may be NULL) / step_constraint: the same for the action
+ *   constraint.  At least one of the two constraints must be given.  The constraint exports are counted like the others and never stop a run.
+ * Every walker keeps a TRIED SET: the enabled instances of the state it stands on, by position in ordinal order, that it has drawn and was refused.  It
+ *   is cleared when the walker moves or starts and kept between launches.  It holds 256 positions; a state with more enabled instances ends the run
+ *   with found = 2, viol_mask = VSRMC_SIM_ERR_TRIED_WIDTH.
+ * THE ITERATION CONTRACT.  A launch ("round") is 64 iterations of every walker.  In one iteration a walker does exactly one of four things:
+ *   start    it has no walk yet, or its depth equals max_depth, or its state has no enabled instance, or every enabled instance has been tried (counted
+ *            in `stuck`: the state is terminal in the constrained model): Init goes into its record, the tried set is cleared.  The state program is
+ *            evaluated on Init and its bits are counted.  No random draw is taken.
+ *   Otherwise it TRIES: one draw of the walker's generator (xorshift64* seeded as in vsrmc_simulate / vsrmc_simulate_where); pick = draw % (total -
+ *            |tried|) over the UNTRIED enabled instances in ordinal order; the instance is generated (an evaluation error ends the run, found = 2); the
+ *            step program is evaluated on the pair (state, successor) before any move.
+ *   blocked  the step_constraint bit is false: the instance is marked tried, `blocked` + 1; nothing else is evaluated or counted, the walker stays.
+ *   Otherwise the walker moves on trial and the state program is evaluated on the successor.
+ *   pruned   the state_constraint bit is false: the walker is put back, the instance is marked tried, `pruned` + 1; its depth is unchanged and the bits of
+ *            both programs are counted nowhere.  With stop = 1 the state bits in pruned_stop_mask (found = 3), then the built-in invariants of that
+ *            successor (found = 1), end the run: ords[0 .. viol_steps) INCLUDES the step into the pruned state — the constrained BFS checks -invariant
+ *            names and the built-in invariants on pruned states too.  pruned_stop_mask = 0: a pruned state's predicates stop nothing.
+ *   step     the move stands: steps, n_pairs (a step program is present) and n_states (a state program is present) + 1, the bits of both programs are
+ *            counted, the tried set is cleared.  With stop = 1: step queries (found = 4), state queries (3), built-in invariants (1), in this order.
+ *   Drawing without replacement up to the first acceptance is uniform over the permitted transitions into in-model states, and a state is left, or
+ *   found stuck, within `total` iterations.
+ * Without a stop: steps + walks + blocked + pruned == 64 * rounds * n_walkers; n_states == steps + walks and count_state[state_constraint] == n_states
+ *   (a state program is present); n_pairs == steps and count_step[step_constraint] == n_pairs (a step program is present).  With max_rounds > 0 every
+ *   count is the same in every run with the same seed.
+ * Init fails the state constraint: nothing is launched and no device is looked at — init_pruned = 1, walks = 0, found = 0, return code 0.
+ * Refused with VSRMC_E_ARG before any device is looked at: neither constraint given; an index the program does not export (or no program to export it);
+ *   a step program as state_prog or a state program as step_prog; a program "compiled for another model"; a constraint's program that reads aux_svc or
+ *   aux_client_acked (the rule of vsrmc_checker_constrain_attach: the walk's model is the constrained search's); max_depth outside 1..512; no walkers. */
+#define VSRMC_SIM_ERR_TRIED_WIDTH 40   /* found = 2: a state has more enabled instances than the tried set has positions (256) */
+typedef struct vsrmc_sim_constrained_result {
+  int32_t found;            /* 0 none, 1 built-in invariant, 2 error, 3 state predicate, 4 step predicate */
+  int32_t viol_mask;        /* found 1/2: as vsrmc_sim_result; found 3/4: the predicate bits of the hit */
+  int32_t viol_steps;
+  uint64_t steps, walks, rounds;
+  uint64_t n_states, n_pairs;              /* evaluations of each program that are counted: states stood on, pairs taken */
+  uint64_t count_state[8], count_step[8];
+  double seconds;
+  uint32_t ords[512];
+  uint64_t blocked, pruned, stuck;         /* tries the action constraint / the state constraint refused; starts out of a state with every instance tried */
+  int32_t init_pruned;                     /* 1: Init fails the state constraint — nothing was walked */
+  int32_t reserved0;
+} vsrmc_sim_constrained_result;
+int32_t vsrmc_simulate_constrained(const vsrmc_model* m, int32_t device, const vsrmc_where* state_prog, int32_t state_constraint,
+                                   const vsrmc_where* step_prog, int32_t step_constraint, uint32_t pruned_stop_mask, int32_t stop, uint32_t n_walkers,
+                                   int32_t max_depth, uint64_t seed, double max_seconds, uint64_t max_rounds, vsrmc_sim_constrained_result* out);
+
 /* ---- sharded seen-set (≙ tlc2.tool.fp.MultiFPSet across GPUs): the phases of one BFS level -----------------------
  * world ranks, one per GPU; owner(fp) = ((fp >> 40) & 0xFFFFFF) % world.  The caller (vsr_tlaplus_amd/sharded.py over
  * torch.distributed / RCCL) owns the exchange buffers and moves them between ranks; every pointer is a device pointer.

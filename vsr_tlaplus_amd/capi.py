@@ -106,6 +106,11 @@ class SimWhereResult(C.Structure):
                 ("count_step", C.c_uint64 * 8), ("seconds", C.c_double), ("ords", C.c_uint32 * 512)]
 
 
+class SimConstrainedResult(C.Structure):
+    _fields_ = SimWhereResult._fields_ + [("blocked", C.c_uint64), ("pruned", C.c_uint64), ("stuck", C.c_uint64), ("init_pruned", C.c_int32),
+                                          ("reserved0", C.c_int32)]
+
+
 # every symbol include/vsrmc.h declares: name -> (restype, argtypes)
 V = C.c_void_p
 SYMBOLS = {
@@ -193,6 +198,8 @@ SYMBOLS = {
     "vsrmc_simulate": (C.c_int32, [V, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.c_double, C.POINTER(SimResult)]),
     "vsrmc_simulate_where": (C.c_int32, [V, C.c_int32, V, V, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.c_double, C.c_uint64,
                                          C.POINTER(SimWhereResult)]),
+    "vsrmc_simulate_constrained": (C.c_int32, [V, C.c_int32, V, C.c_int32, V, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64,
+                                               C.c_double, C.c_uint64, C.POINTER(SimConstrainedResult)]),
     "vsrmc_checker_probe": (C.c_int32, [V, C.POINTER(LevelInfo)]),
     "vsrmc_checker_probe2": (C.c_int32, [V, C.POINTER(LevelInfo), C.POINTER(LevelInfo)]),
     "vsrmc_checker_probe3": (C.c_int32, [V, C.POINTER(LevelInfo), C.POINTER(LevelInfo), C.POINTER(LevelInfo)]),

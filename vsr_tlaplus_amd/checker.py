@@ -277,6 +277,39 @@ class Model:
             out["trace"] = self.replay(out["ordinals"], device)
         return out
 
+    def simulate_constrained(self, state=None, constraint=None, step=None, action_constraint=None, pruned_stop=(), stop=True, n_walkers=1 << 16,
+                             max_depth=100, seed=1, max_seconds=10.0, max_rounds=0, device=0):
+        """Random walks under a state constraint and / or an action constraint (k_simulate_constrained; the iteration contract: include/vsrmc.h): a walk
+        moves only along permitted transitions into in-model states.  `state`: a Where of compile_predicates whose export `constraint` (a name or a
+        number, as ModelChecker.constrain takes it; None: no state constraint) is the state constraint, every other export a query as in simulate_where;
+        `step` / `action_constraint`: the same with a Where of compile_step_predicates.  At least one constraint.  `pruned_stop`: the exports of `state`
+        (names or numbers, or a ready mask) that also end a stop=True run when they hold on a PRUNED successor (found 3; the walk includes the step
+        into it).  -> the dict of simulate_where plus blocked, pruned, stuck, init_pruned (True: Init fails the constraint, nothing was walked)."""
+        def index_of(where, name, what):
+            if name is None:
+                return -1
+            if where is None:
+                raise ValueError("%s=%r needs the program that exports it" % (what, name))
+            return name if isinstance(name, int) else where.names.index(name)
+        ks, kp = index_of(state, constraint, "constraint"), index_of(step, action_constraint, "action_constraint")
+        mask = pruned_stop if isinstance(pruned_stop, int) else sum(1 << index_of(state, nm, "pruned_stop") for nm in pruned_stop)
+        r = capi.SimConstrainedResult()
+        check(capi.load().vsrmc_simulate_constrained(self._h, device, state._h if state is not None else None, ks, step._h if step is not None else None, kp,
+                                                     mask, int(bool(stop)), n_walkers, max_depth, C.c_uint64(int(seed) & (2 ** 64 - 1)), max_seconds,
+                                                     max_rounds, C.byref(r)))
+        sn = list(state.names) if state is not None else []
+        pn = list(step.names) if step is not None else []
+        out = dict(found=r.found, viol_mask=r.viol_mask, viol_steps=r.viol_steps, steps=r.steps, walks=r.walks, rounds=r.rounds, n_states=r.n_states,
+                   n_pairs=r.n_pairs, seconds=r.seconds, state_names=sn, step_names=pn, count_state={nm: int(r.count_state[k]) for k, nm in enumerate(sn)},
+                   count_step={nm: int(r.count_step[k]) for k, nm in enumerate(pn)}, blocked=r.blocked, pruned=r.pruned, stuck=r.stuck,
+                   init_pruned=bool(r.init_pruned), hit=None, ordinals=None, trace=None)
+        if r.found in (3, 4):
+            out["hit"] = [nm for k, nm in enumerate(sn if r.found == 3 else pn) if (r.viol_mask >> k) & 1]
+        if r.found in (1, 3, 4):
+            out["ordinals"] = [int(r.ords[k]) for k in range(r.viol_steps)]
+            out["trace"] = self.replay(out["ordinals"], device)
+        return out
+
     def replay(self, ords, device=0):
         """Re-execute a path of ordinals from Init on the GPU -> [(action name, wire record)]."""
         n = len(ords)

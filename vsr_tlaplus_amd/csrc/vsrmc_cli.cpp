@@ -73,6 +73,14 @@ static void usage() {
       "                    run with its behaviour; exit codes as above (12 violated, 0 reached, 14 not met).  With -whereReport / -stepReport the exported\n"
       "                    predicates are counted over the walks instead, without stopping; -simRounds N: exactly N rounds of 64 steps per walker (the\n"
       "                    counts are then the same in every run with the same seed) instead of -maxSeconds\n"
+      "  -walkConstraint NAME    with -simulate and -predicates FILE: the exported predicate NAME is a state constraint on the walks (TLC's simulator honours\n"
+      "                    CONSTRAINT): a walker never moves into a state that fails it; Init is subject to it.  A walker draws among the enabled instances it\n"
+      "                    has not been refused yet, so it leaves a state, or finds it terminal in the constrained model, within as many tries as the state\n"
+      "                    has instances.  -invariant NAMES (and the built-in invariants) are checked on the refused successors as well, as -constraint does\n"
+      "  -walkActionConstraint NAME  with -simulate and -steps FILE: the exported step predicate NAME is an action constraint on the walks (ACTION_CONSTRAINT):\n"
+      "                    a transition that fails it is never taken.  Both combine with each other and with -reach, -invariant, -stepReach, -stepInvariant,\n"
+      "                    -whereReport, -stepReport, -simRounds and -dumpTrace; with no query at all the built-in invariants are checked on the constrained\n"
+      "                    walks.  A closing line gives the tries blocked, the tries pruned and the walks that ended stuck.  Not with -json\n"
       "  -validateTrace F  read a TLC trace (trace expression, or console \"State k:\" form) and check on the GPU that it is a\n"
       "                    behaviour of the model: Init, then one generated successor after the other; reports the invariants\n"
       "                    its last state violates\n"
@@ -158,8 +166,10 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
-  bool deep_predicates = false, constrained = false, action_constrained = false;
+  bool deep_predicates = false, constrained = false, action_constrained = false, walk_constrained = false, walk_action_constrained = false;
   for (int i = 1; i < argc; i++) {
+    if (std::string(argv[i]) == "-walkConstraint") walk_constrained = true;
+    if (std::string(argv[i]) == "-walkActionConstraint") walk_action_constrained = true;
     if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
     if (std::string(argv[i]) == "-constraint") constrained = true;
     if (std::string(argv[i]) == "-actionConstraint") action_constrained = true;
@@ -171,7 +181,7 @@ int main(int argc, char** argv) {
       if (action_constrained) { std::fprintf(stderr, "Error: -actionConstraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
       return exec_sharded(argc, argv, i);
     }
-  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, constraint_arg, action_constraint_arg, steps_file, step_reach_arg, step_invariant_arg;
+  std::string cfg, tla, trace_file, chk_file, recover_file, dump_file, dump_trace_file, predicates_file, reach_arg, invariant_arg, constraint_arg, action_constraint_arg, walk_constraint_arg, walk_action_constraint_arg, steps_file, step_reach_arg, step_invariant_arg;
   bool where_report = false, step_report = false;
   unsigned long long dump_max = 1000000ull, dumped = 0;
   double chk_minutes = 30.0;
@@ -224,6 +234,8 @@ int main(int argc, char** argv) {
     else if (a == "-whereReport") where_report = true;
     else if (a == "-constraint" && i + 1 < argc) constraint_arg = argv[++i];
     else if (a == "-actionConstraint" && i + 1 < argc) action_constraint_arg = argv[++i];
+    else if (a == "-walkConstraint" && i + 1 < argc) walk_constraint_arg = argv[++i];
+    else if (a == "-walkActionConstraint" && i + 1 < argc) walk_action_constraint_arg = argv[++i];
     else if (a == "-steps" && i + 1 < argc) steps_file = argv[++i];
     else if (a == "-stepReach" && i + 1 < argc) step_reach_arg = argv[++i];
     else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
@@ -237,7 +249,7 @@ int main(int argc, char** argv) {
   if (constrained) {                                              // refused before any device call
     const char* why = constraint_arg.empty() ? "-constraint needs a NAME"
                       : predicates_file.empty() ? "-constraint NAME needs -predicates FILE"
-                      : simulate ? "-constraint belongs to the exhaustive search: a random walk (-simulate) is not constrained"
+                      : simulate ? "-constraint belongs to the exhaustive search: a random walk (-simulate) is not constrained: use -walkConstraint NAME"
                       : deep_predicates ? "-constraint cannot be combined with -deepPredicates: the levels beyond the record buffers are not constrained"
                       : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-constraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
                       : (!chk_file.empty() || !recover_file.empty()) ? "-constraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
@@ -247,11 +259,20 @@ int main(int argc, char** argv) {
   if (action_constrained) {                                       // refused before any device call
     const char* why = action_constraint_arg.empty() ? "-actionConstraint needs a NAME"
                       : steps_file.empty() ? "-actionConstraint NAME needs -steps FILE"
-                      : simulate ? "-actionConstraint belongs to the exhaustive search: a random walk (-simulate) is not constrained"
+                      : simulate ? "-actionConstraint belongs to the exhaustive search: a random walk (-simulate) is not constrained: use -walkActionConstraint NAME"
                       : deep_predicates ? "-actionConstraint cannot be combined with -deepPredicates: the levels beyond the record buffers are not constrained"
                       : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-actionConstraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
                       : (!chk_file.empty() || !recover_file.empty()) ? "-actionConstraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
                       : audit ? "-actionConstraint cannot be combined with -audit" : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
+  if (walk_constrained || walk_action_constrained) {              // refused before any device call
+    const char* why = walk_constrained && walk_constraint_arg.empty() ? "-walkConstraint needs a NAME"
+                      : walk_action_constrained && walk_action_constraint_arg.empty() ? "-walkActionConstraint needs a NAME"
+                      : !simulate ? "-walkConstraint / -walkActionConstraint belong to -simulate: the exhaustive search takes -constraint NAME / -actionConstraint NAME"
+                      : walk_constrained && predicates_file.empty() ? "-walkConstraint NAME needs -predicates FILE"
+                      : walk_action_constrained && steps_file.empty() ? "-walkActionConstraint NAME needs -steps FILE"
+                      : json ? "-walkConstraint / -walkActionConstraint cannot be combined with -json" : nullptr;
     if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
   }
   if (deep_predicates) {                                          // refused before any device call
@@ -349,7 +370,12 @@ int main(int argc, char** argv) {
   vsrmc_where *s_all = nullptr, *s_query = nullptr;
   std::vector<std::string> step_names, step_query_names;
   size_t n_step_reach = 0;
-  if (!step_reach_arg.empty() || !step_invariant_arg.empty() || step_report) {
+  // -walkConstraint / -walkActionConstraint (with -simulate): `w_walk` / `s_walk` = the query program of the kind (may have no query) with the constraint
+  // as one more exported predicate behind the queries, at index walk_con / walk_act; a report counts over w_all / s_all, where the constraint is the
+  // export of its own name, at index walk_con_all / walk_act_all
+  vsrmc_where *w_walk = nullptr, *s_walk = nullptr;
+  int walk_con = -1, walk_act = -1, walk_con_all = -1, walk_act_all = -1;
+  if (!step_reach_arg.empty() || !step_invariant_arg.empty() || step_report || walk_action_constrained) {
     if (steps_file.empty()) { std::fprintf(stderr, "Error: -stepReach / -stepInvariant / -stepReport need -steps FILE\n"); return 2; }
     std::ifstream pf(steps_file, std::ios::binary);
     if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", steps_file.c_str()); return 1; }
@@ -373,6 +399,17 @@ int main(int argc, char** argv) {
       }
       if (vsrmc_step_predicates_compile(m, local.c_str(), &s_query) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
+    if (walk_action_constrained) {
+      for (size_t k = 0; k < step_names.size(); k++)
+        if (step_names[k] == walk_action_constraint_arg) walk_act_all = (int)k;
+      if (walk_act_all < 0) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", steps_file.c_str(), walk_action_constraint_arg.c_str()); return 2; }
+      if (step_query_names.size() > 7) { std::fprintf(stderr, "Error: -walkActionConstraint with more than 7 -stepReach / -stepInvariant names\n"); return 2; }
+      std::string local = make_local(text);
+      for (size_t k = 0; k < step_query_names.size(); k++) local += "\nQuery" + std::to_string(k) + " == " + (k < n_step_reach ? "" : "~") + step_query_names[k];
+      local += "\nWalkActionConstraintQuery == " + walk_action_constraint_arg;
+      walk_act = (int)step_query_names.size();
+      if (vsrmc_step_predicates_compile(m, local.c_str(), &s_walk) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+    }
   }
   // -actionConstraint NAME: a program of its own over the same file, every definition LOCAL and the constraint its one exported predicate
   vsrmc_where* s_act = nullptr;
@@ -393,7 +430,7 @@ int main(int argc, char** argv) {
     const std::string local = make_local(text) + "\nActionConstraintQuery == " + action_constraint_arg;
     if (vsrmc_step_predicates_compile(m, local.c_str(), &s_act) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
   }
-  if (!reach_arg.empty() || !invariant_arg.empty() || where_report || constrained) {
+  if (!reach_arg.empty() || !invariant_arg.empty() || where_report || constrained || walk_constrained) {
     if (predicates_file.empty()) { std::fprintf(stderr, "Error: -reach / -invariant / -whereReport need -predicates FILE\n"); return 2; }
     std::ifstream pf(predicates_file, std::ios::binary);
     if (!pf) { std::fprintf(stderr, "Error: cannot read %s\n", predicates_file.c_str()); return 1; }
@@ -429,6 +466,17 @@ int main(int argc, char** argv) {
       con_index = (int)con_inv_names.size();
       if (vsrmc_predicates_compile(m, local.c_str(), &w_con) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
     }
+    if (walk_constrained) {
+      for (size_t k = 0; k < where_names.size(); k++)
+        if (where_names[k] == walk_constraint_arg) walk_con_all = (int)k;
+      if (walk_con_all < 0) { std::fprintf(stderr, "Error: %s exports no predicate %s\n", predicates_file.c_str(), walk_constraint_arg.c_str()); return 2; }
+      if (query_names.size() > 7) { std::fprintf(stderr, "Error: -walkConstraint with more than 7 -reach / -invariant names\n"); return 2; }
+      std::string local = make_local(text);
+      for (size_t k = 0; k < query_names.size(); k++) local += "\nQuery" + std::to_string(k) + " == " + (k < n_reach ? "" : "~") + query_names[k];
+      local += "\nWalkConstraintQuery == " + walk_constraint_arg;
+      walk_con = (int)query_names.size();
+      if (vsrmc_predicates_compile(m, local.c_str(), &w_walk) != 0) { std::fprintf(stderr, "Error: %s\n", vsrmc_last_error()); return 1; }
+    }
   }
   if (simulate) {   // ≙ tlc2.TLC -simulate -depth N
     // the walk Init .. ords[n_steps), printed the way the BFS prints a behaviour
@@ -462,8 +510,11 @@ int main(int argc, char** argv) {
       if (w_query) vsrmc_where_destroy(w_query);
       if (s_all) vsrmc_where_destroy(s_all);
       if (s_query) vsrmc_where_destroy(s_query);
+      if (w_walk) vsrmc_where_destroy(w_walk);
+      if (s_walk) vsrmc_where_destroy(s_walk);
       vsrmc_model_destroy(m);
     };
+    const bool walk_any = walk_constrained || walk_action_constrained;
     if (!w_all && !s_all) {                                         // no question of the user's: the built-in invariants alone (k_simulate)
       if (!predicates_file.empty() || !steps_file.empty() || sim_rounds) {
         std::fprintf(stderr, "Error: -simulate: -predicates FILE needs -reach / -invariant / -whereReport, -steps FILE needs -stepReach / -stepInvariant / -stepReport, "
@@ -498,12 +549,29 @@ int main(int argc, char** argv) {
     std::printf("Running Random Simulation with seed %llu: %u walkers on the GPU, depth %d.\n", sim_seed, sim_walkers, sim_depth);
     int code = 0;
     vsrmc_sim_where_result r;
+    vsrmc_sim_constrained_result rc;
     auto totals = [&]() {
       std::printf("%llu states and %llu steps evaluated in %llu walks, %llu rounds, %.3f s (%.3g steps/s).\n", (unsigned long long)r.n_states, (unsigned long long)r.n_pairs,
                   (unsigned long long)r.walks, (unsigned long long)r.rounds, r.seconds, r.seconds > 0 ? (double)r.steps / r.seconds : 0.0);
+      if (walk_any)
+        std::printf("Walk constraints: %llu tries blocked by the action constraint, %llu tries pruned by the state constraint, %llu walks ended stuck (every enabled "
+                    "instance refused); %llu steps taken.\n", (unsigned long long)rc.blocked, (unsigned long long)rc.pruned, (unsigned long long)rc.stuck,
+                    (unsigned long long)rc.steps);
+    };
+    // one run: under the walk constraints (k_simulate_constrained; `r` gets the fields the two results share) or as before (k_simulate_where)
+    auto run_walks = [&](const vsrmc_where* ws, int ks, const vsrmc_where* wp, int kp, uint32_t pruned_stop, int stop) -> int {
+      if (!walk_any) return vsrmc_simulate_where(m, device, ws, wp, stop, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &r);
+      const int code = vsrmc_simulate_constrained(m, device, ws, ks, wp, kp, pruned_stop, stop, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &rc);
+      if (code != 0) return code;
+      r.found = rc.found; r.viol_mask = rc.viol_mask; r.viol_steps = rc.viol_steps;
+      r.steps = rc.steps; r.walks = rc.walks; r.rounds = rc.rounds; r.n_states = rc.n_states; r.n_pairs = rc.n_pairs; r.seconds = rc.seconds;
+      for (int k = 0; k < 8; k++) { r.count_state[k] = rc.count_state[k]; r.count_step[k] = rc.count_step[k]; }
+      for (int k = 0; k < 512; k++) r.ords[k] = rc.ords[k];
+      if (rc.init_pruned) std::printf("The initial state fails the constraint %s: there is nothing to walk.\n", walk_constraint_arg.c_str());
+      return 0;
     };
     if (where_report || step_report) {
-      if (vsrmc_simulate_where(m, device, where_report ? w_all : nullptr, step_report ? s_all : nullptr, 0, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &r) != 0) {
+      if (run_walks((where_report || walk_constrained) ? w_all : nullptr, walk_con_all, (step_report || walk_action_constrained) ? s_all : nullptr, walk_act_all, 0, 0) != 0) {
         std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
         return 1;
       }
@@ -529,8 +597,11 @@ int main(int argc, char** argv) {
       }
       totals();
     }
-    if ((w_query || s_query) && code == 0) {
-      if (vsrmc_simulate_where(m, device, w_query, s_query, 1, sim_walkers, sim_depth, sim_seed, sim_seconds, sim_rounds, &r) != 0) {
+    // under a walk constraint a run with no query and no report still walks: the built-in invariants on the constrained walks
+    if ((w_query || s_query || (walk_any && !where_report && !step_report)) && code == 0) {
+      uint32_t pruned_stop = 0;                                     // the -invariant names: checked on the states the constraint prunes as well
+      for (size_t k = n_reach; walk_constrained && k < query_names.size(); k++) pruned_stop |= 1u << k;
+      if (run_walks(walk_constrained ? w_walk : w_query, walk_con, walk_action_constrained ? s_walk : s_query, walk_act, pruned_stop, 1) != 0) {
         std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
         return 1;
       }
