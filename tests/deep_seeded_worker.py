@@ -119,6 +119,25 @@ def make_checker(vt, case, exact, frontier_words=None, generous=False):
     return m, mc
 
 
+def check_records(case, mc, by_fp, label):
+    """every record of the newest level (mc.frontier()): the oracle's record of that fingerprint (under the winning auxkey), bag order aside.  by_fp: fingerprint
+    -> [(auxkey, producer number, successor, ..)] of exactly the states the level must hold; case: what gives orc, P and norm().  Shared with
+    tests/constrained_seeded_worker.py, where by_fp holds the PERMITTED producers of the states the state constraint keeps."""
+    words, off = mc.frontier()
+    assert len(off) - 1 == len(by_fp), (label, len(off) - 1, len(by_fp))
+    seen = set()
+    for k in range(len(off) - 1):
+        rec = words[int(off[k]): int(off[k + 1])]
+        fp, ak = case.orc.fingerprint(case.P, rec)
+        cands = by_fp.get(fp)
+        assert cands, (label, "a record of the level is no successor of a seed", k)
+        best = min(c[0] for c in cands)
+        assert ak == best, (label, "the smallest canonical auxkey wins", k, ak, best)
+        assert case.norm(rec) in set(case.norm(c[2]["words"]) for c in cands if c[0] == best), (label, "record", k, fp)
+        seen.add(fp)
+    assert len(seen) == len(by_fp), label
+
+
 def check_level(vt, case, mc, d, label, n_traces=48):
     """everything a stored step over the seeds must have left, against the oracle"""
     assert d["level"] == 2 and d["error_code"] == 0, (label, d)
@@ -135,19 +154,8 @@ def check_level(vt, case, mc, d, label, n_traces=48):
         s_ = (s_ + f) & M64
     assert mc.level_checksum() == (x, s_, len(case.new)), label
     # every record of the level: the oracle's record of that fingerprint (under the winning auxkey), bag order aside
-    words, off = mc.frontier()
-    assert len(off) - 1 == len(case.new)
-    seen = set()
-    for k in range(len(off) - 1):
-        rec = words[int(off[k]): int(off[k + 1])]
-        fp, ak = case.orc.fingerprint(case.P, rec)
-        cands = case.by_fp.get(fp)
-        assert cands, (label, "a record of the level is no successor of a seed", k)
-        best = min(a for a, _i, _s in cands)
-        assert ak == best, (label, "the smallest canonical auxkey wins", k, ak, best)
-        assert case.norm(rec) in set(case.norm(s["words"]) for a, _i, s in cands if a == best), (label, k)
-        seen.add(fp)
-    assert len(seen) == len(case.new)
+    assert len(case.by_fp) == len(case.new)
+    check_records(case, mc, case.by_fp, label)
     # violations
     if case.viol:
         vfp = min(case.viol)

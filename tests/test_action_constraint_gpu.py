@@ -191,7 +191,8 @@ def test_timers_in_view_1_exhausts(vt, refs):
 # 5. TRUE: the plain search.  (3,1,{v1,v2},1), levels 1-12: against the plain checker and the Python reference, level by level — tests/golden has no level
 #    file of that space (oracle_levels_*.json are configs 2, 3, 4, 5 and the analysis models, and bfs_counts.json has no (3,1,{v1,v2},1) either), so the comparison against golden files runs on the spaces
 #    that have one: the first 10 levels of config 2 (3,1,{v1,v2},2), the first 7 of config 5 (five replicas) and of config 4 (two clients, policy
-#    assume_commit_number).  This is the only place k_step_expand meets five replicas and two clients.
+#    assume_commit_number).  Here k_step_expand meets five replicas and two clients near Init, where nothing is blocked and counts and checksums are compared;
+#    test_constrained_seeded_gpu.py runs it on harvested states of (5,1,2,1), (4,1,2,1) and (3,2,3,1) under constraints that block, record by record.
 # ---------------------------------------------------------------------------------------------------------------------
 def test_true_equals_the_plain_checker(vt, refs):
     ref = refs("true-3121")

@@ -134,6 +134,25 @@ int constraint_restart(vsrmc_checker* c) {
   return constrain_level(c, nullptr);
 }
 
+#ifdef VSRMC_TEST_HOOKS
+// TEST HOOK (host_test_seed.hpp): level 1 of a seeded search is the caller's records, subject to no constraint — what constraint_restart has just made of Init
+// (its level-1 figures, a pruned Init's seen-set slot in table_pruned, its count in hist_new) goes, the attachment stays
+void constraint_forget_init(vsrmc_checker* c) {
+  c->table_pruned = 0;
+  c->hist_new[1] = 0;
+  vsrmc_constraint* a = c->constraint;
+  if (!a) return;
+  a->levels.clear();
+  a->pruned_fps.clear();
+  a->pruned_total = 0;
+  a->pruned_held = 0;
+  a->pruned_fetched = true;
+  a->write_ratio = 1.0;
+  a->pruned_level = 0;
+  a->beyond = 0;
+}
+#endif
+
 }  // namespace
 
 extern "C" {

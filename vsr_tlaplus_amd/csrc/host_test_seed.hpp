@@ -10,6 +10,7 @@
 #ifdef VSRMC_TEST_HOOKS
 
 namespace {
+void constraint_forget_init(vsrmc_checker* c);                  // (host_constrain.hpp)
 // one claim per record at level 1 (k_seed for many records): the records are in device layout with their view hashes filled in
 __global__ void k_seed_many(Model M, const u64* words, const u64* refs, u64 n, Slot* table, u64 tmask, u64* lvl_fp, u32* err) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -33,6 +34,8 @@ extern "C" {
 // parent), refs, level fingerprints, frontier counters.  Refuses, without launching anything, a record whose length is not the layout's
 // (VSRMC_E_ARG) or whose bag is larger than the layout allows (VSRMC_E_REP), two records of one fingerprint (VSRMC_E_ARG) and more records or words
 // than the checker's buffers hold (VSRMC_E_ARG).  vsrmc_checker_reset goes back to Init.
+// A state constraint and an action constraint stay attached (attach first, then seed: both attach calls put Init back) and their results start over.  The
+// seeds are level 1 AS GIVEN, subject to neither constraint: no seed is pruned, and what checker_seed's filter made of Init is forgotten with Init.
 int32_t vsrmc_test_checker_seed_records(vsrmc_checker* c, const uint64_t* words, const uint64_t* off, uint64_t n) {
   if (!c || !words || !off || n == 0) return fail(VSRMC_E_ARG, "NULL argument / no record");
   if (c->opt.world != 1) return fail(VSRMC_E_STATE, "seeding is for unsharded checkers");
@@ -95,6 +98,7 @@ int32_t vsrmc_test_checker_seed_records(vsrmc_checker* c, const uint64_t* words,
   c->total_generated = 0;
   c->cur_max_bag = max_bag;
   c->bag_known = true;
+  constraint_forget_init(c);                                     // (Init's level-1 figures, table_pruned and hist_new of a pruned or kept Init: not this level's)
   // traces of a seeded search start at a seed, not at Init (host_checkpoint.hpp: replay_path): the records are kept, addressed by fingerprint
   c->test_seed_index.resize(n);
   for (u64 i = 0; i < n; i++) c->test_seed_index[i] = {fps[i], i};
