@@ -625,6 +625,52 @@ int32_t vsrmc_checker_deep_step_pairs(vsrmc_checker* c, int32_t level, uint64_t*
 int32_t vsrmc_checker_deep_witness(vsrmc_checker* c, int32_t level, int32_t which_program, int32_t k, uint64_t* words, uint64_t cap_words, uint64_t* off,
                                    int32_t* actions, uint64_t cap_states, uint64_t* n_states);
 
+/* The deadlock check on the levels beyond the record buffers (csrc/host_deep_terminal.hpp).  vsrmc_checker_terminal_scan reads the newest
+ * STORED level and refuses a seen-set-only one; the TERMINAL ATTACHMENT makes the check reach as deep as the built-in invariants do.  It is independent of
+ * vsrmc_checker_deep_attach and combines with it (k_step_list then runs once for each on a sub-slice of the inserted level: the lists are not shared).
+ * Without the attachment every call, count and exit code is what it was; with it the search itself (level infos, checksums, violations) is untouched.
+ * vsrmc_checker_deep_terminal_attach: VSRMC_E_STATE on a sharded checker (world > 1), on an exact_ties checker and while a state or an action constraint
+ *   is attached (and those attachments are refused while this one is; vsrmc_checker_probe2 / _probe3 are refused as well).  A second attachment is a
+ *   no-op.  Its buffers are allocated once, here: one TermCtl per level of a descent (512), two lists of 2^20 entries, an instance list of 2^22 entries,
+ *   and the child chunk (2^26 words of records with their refs / fingerprints / keys); VSRMC_E_HIP when the device has no room, and nothing is changed.
+ *   Each seen-set-only level K is scanned EXACTLY ONCE by k_terminal, in the first descent after the attachment whose scratch buffers its records pass
+ *   through (the rule of vsrmc_checker_deep_attach, a late attachment, one after vsrmc_checker_load and a re-basing descent included), as a regenerated
+ *   (kind 0) or the inserted level (kind 1).  The attachment is NOT part of a checkpoint; vsrmc_checker_reset keeps it and forgets its results.
+ *   The probed level (kind 2) has no records: k_probe_children (csrc/vsr_deep_terminal.hpp) writes the successors of every sub-slice of the inserted level
+ *   that the seen-set does not hold into the child chunk, chunk by chunk, and k_terminal reads each chunk.  When the pass is over the terminal copies that
+ *   are states of the inserted level after all are dropped and the rest de-duplicated by fingerprint (the copy with the smallest key stands for the
+ *   state).  A violation of a built-in invariant in the inserted level ends the examination there: that pass reports no probed level.
+ * vsrmc_checker_deep_terminal_levels: the contract of vsrmc_checker_deep_levels.
+ * vsrmc_checker_deep_terminal_result: kinds 0 and 1: every figure exact (n_terminal == `deadlocks` of the pass that expands the level).  Kind 2: n_states =
+ *   the COPIES scanned (one state arrives from several parents); n_terminal / n_unsettled / the minima = DISTINCT states of the probed level, exact while the
+ *   list of terminal copies did not overflow (exact = 1), otherwise lower bounds (exact = 0; n_listed = the copies offered).  ms / children_ms: HOST times
+ *   around the launches (k_terminal and its read-back; kind 2: k_step_list + k_probe_children beside it), synchronisation included.
+ * vsrmc_checker_deep_terminal_states: the contract of vsrmc_checker_terminal_states (fingerprints ascending, flag bytes; VSRMC_E_REP with *n = the true
+ *   number when the list overflowed).  Lists of all scanned levels are kept.  Test knobs, read at the attachment: VSRMC_TERMINAL_LIST_CAP=N lowers the 2^20,
+ *   VSRMC_DEEP_CHILD_WORDS=N the child chunk (at least 64 records of the largest size), so that a sub-slice
+ *   takes several chunks; VSRMC_STEP_SLICE is read at every slice.
+ * vsrmc_checker_deep_terminal_witness: the behaviour Init .. the terminal state (unsettled != 0: the unsettled terminal state) with the smallest
+ *   fingerprint of that level, the layout of vsrmc_checker_trace.  Kinds 0 / 1: vsrmc_checker_trace_fp.  Kind 2: the parent named by the 45 bits the
+ *   state's smallest key keeps, then the state (n_states = level). */
+typedef struct vsrmc_deep_terminal_info {
+  int32_t level, kind;                             /* kind: 0 regenerated, 1 inserted, 2 probed */
+  int32_t exact, reserved0;                        /* 0 (kind 2 only): n_terminal / n_unsettled are lower bounds */
+  uint64_t slices;                                 /* scratch slices scanned (kind 2: instance lists of sub-slices consumed) */
+  uint64_t chunks;                                 /* k_terminal launches over records (kind 2: k_probe_children launches) */
+  uint64_t n_states;                               /* states scanned (kind 2: n_copies) */
+  uint64_t n_terminal, n_unsettled;
+  uint64_t min_fp, min_fp_unsettled;               /* ~0 = none */
+  uint64_t n_listed;                               /* what vsrmc_checker_deep_terminal_states reports as *n */
+  uint64_t bytes_written;                          /* kind 2: bytes k_probe_children wrote (records, refs, fingerprints, keys) */
+  double ms, children_ms;
+} vsrmc_deep_terminal_info;
+int32_t vsrmc_checker_deep_terminal_attach(vsrmc_checker* c);
+int32_t vsrmc_checker_deep_terminal_levels(vsrmc_checker* c, int32_t* levels, int32_t* probed, uint64_t cap, uint64_t* n);
+int32_t vsrmc_checker_deep_terminal_result(vsrmc_checker* c, int32_t level, int32_t probed, vsrmc_deep_terminal_info* info);
+int32_t vsrmc_checker_deep_terminal_states(vsrmc_checker* c, int32_t level, int32_t probed, uint64_t* fps, uint8_t* flags, uint64_t cap, uint64_t* n);
+int32_t vsrmc_checker_deep_terminal_witness(vsrmc_checker* c, int32_t level, int32_t probed, int32_t unsettled, uint64_t* words, uint64_t cap_words,
+                                            uint64_t* off, int32_t* actions, uint64_t cap_states, uint64_t* n_states);
+
 /* ≙ TLC's checkpoints (ModelChecker.checkpoint → FPSet.beginChkpt/commitChkpt, StateQueue and TLCTrace checkpoints; `-recover`):
  * one file holds the search between two levels — the occupied seen-set slots, the newest stored frontier, what the automatic level scheme
  * has learnt and, once the search has gone beyond the record buffers (vsrmc_checker_deepen), the descriptors of the levels that exist in

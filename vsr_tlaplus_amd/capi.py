@@ -80,6 +80,12 @@ class DeepInfo(C.Structure):
                 ("slices", C.c_uint64), ("n_hit_states", C.c_uint64), ("n_hit_pairs", C.c_uint64), ("where_ms", C.c_double), ("step_ms", C.c_double)]
 
 
+class DeepTerminalInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("kind", C.c_int32), ("exact", C.c_int32), ("reserved0", C.c_int32), ("slices", C.c_uint64), ("chunks", C.c_uint64),
+                ("n_states", C.c_uint64), ("n_terminal", C.c_uint64), ("n_unsettled", C.c_uint64), ("min_fp", C.c_uint64), ("min_fp_unsettled", C.c_uint64),
+                ("n_listed", C.c_uint64), ("bytes_written", C.c_uint64), ("ms", C.c_double), ("children_ms", C.c_double)]
+
+
 class ShardIO(C.Structure):
     _fields_ = [("cand_send", C.c_void_p), ("cand_cap", C.c_uint64)]
 
@@ -189,6 +195,11 @@ SYMBOLS = {
     "vsrmc_checker_deep_where_states": (C.c_int32, [V, C.c_int32, C.c_int32, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_checker_deep_step_pairs": (C.c_int32, [V, C.c_int32, V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_checker_deep_witness": (C.c_int32, [V, C.c_int32, C.c_int32, C.c_int32, V, C.c_uint64, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_terminal_attach": (C.c_int32, [V]),
+    "vsrmc_checker_deep_terminal_levels": (C.c_int32, [V, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_terminal_result": (C.c_int32, [V, C.c_int32, C.c_int32, C.POINTER(DeepTerminalInfo)]),
+    "vsrmc_checker_deep_terminal_states": (C.c_int32, [V, C.c_int32, C.c_int32, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_deep_terminal_witness": (C.c_int32, [V, C.c_int32, C.c_int32, C.c_int32, V, C.c_uint64, V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_check": (C.c_int32, [V, C.c_int32, C.c_double, C.POINTER(C.c_int32), C.POINTER(LevelInfo)]),
     "vsrmc_queue_create": (C.c_int32, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(V)]),
     "vsrmc_queue_enqueue_batch": (C.c_int32, [V, V, V, C.c_uint64]),

@@ -786,7 +786,11 @@ class ModelChecker:
         deep=True: the predicates are also ATTACHED (deep_attach) — one state program (`never` or `reach`, not both) and one step program (`step_never` or
         `step_reach`) — so that the levels beyond the record buffers are examined as well; the run ends at the advance() that finds a hit.  The shallowest
         level wins; within a level a built-in violation, then never, reach, step_never, step_reach.  self.witness then has `kind_of_level` in
-        ("regenerated", "inserted", "probed") and index None (a step hit: no ordinal either); deep_witness_trace() is the behaviour."""
+        ("regenerated", "inserted", "probed") and index None (a step hit: no ordinal either); deep_witness_trace() is the behaviour.
+        check_deadlock=True with deep=True (valid without a predicate): the terminal attachment (deep_terminal_attach) looks for terminal states on the
+        levels beyond the record buffers too, the probed level included; the run ends with "deadlock" at the advance() whose results hold one.
+        self.deadlock then has `kind_of_level` and `exact` besides (min_index None); deadlock_trace() is the behaviour.  Within a level a deadlock comes
+        after a built-in violation and before the predicates; the shallowest level wins, also against a built-in violation found deeper by the same pass."""
         import time
         t0 = time.time()
         if never is not None and self._constraint is not None:
@@ -802,10 +806,14 @@ class ModelChecker:
                 raise ValueError("run(deep=True) attaches one step program: step_never or step_reach")
             deep_state = (never, "violation", 1) if never is not None else (reach, "reached", 2) if reach is not None else None
             deep_step = (step_never, "violation", 3) if step_never is not None else (step_reach, "reached", 4) if step_reach is not None else None
-            if deep_state is None and deep_step is None:
-                raise ValueError("run(deep=True) needs a predicate")
-            self.deep_attach(deep_state[0] if deep_state else None, deep_step[0] if deep_step else None)
+            if deep_state is None and deep_step is None and not check_deadlock:
+                raise ValueError("run(deep=True) needs a predicate or check_deadlock=True")
+            if deep_state is not None or deep_step is not None:
+                self.deep_attach(deep_state[0] if deep_state else None, deep_step[0] if deep_step else None)
+            if check_deadlock:
+                self.deep_terminal_attach()
             self._deep_seen = set()
+            self._deep_term_seen = set()
         while True:
             if max_depth is not None and self.depth >= max_depth:
                 return "max-depth"
@@ -845,7 +853,7 @@ class ModelChecker:
             if never is not None and self._never_on_pruned(never):
                 return "violation"
             if deep and kind == "deep":
-                hit = self._deep_first_hit(deep_state, deep_step, stop_on_violation)
+                hit = self._deep_first_hit(deep_state, deep_step, stop_on_violation, check_deadlock)
                 if hit is not None:
                     return hit
             if d["n_new"] == 0:
@@ -869,12 +877,24 @@ class ModelChecker:
         self.witness = dict(level=r["level"], k=never.names.index(hits[0]), name=hits[0], fp=r["pruned_min_fp_k"][hits[0]], index=None, kind="violation", pruned=True)
         return True
 
-    def _deep_first_hit(self, deep_state, deep_step, stop_on_violation):
-        """the results of the levels the last advance() examined for the first time -> the run's verdict, or None"""
+    def _deep_first_hit(self, deep_state, deep_step, stop_on_violation, check_deadlock=False):
+        """the results of the levels the last advance() examined for the first time -> the run's verdict, or None.  The shallowest level wins; within a
+        level a built-in violation (0), a deadlock (0.5), then the predicates in their order (1 .. 4)."""
         best = None
         if self.violation is not None and stop_on_violation:
             best = (self.violation["level"], 0, None, "violation")
-        for r in self.deep_results():
+        deadlock = None
+        for r in (self.deep_terminal_results() if check_deadlock else ()):
+            key = (r["level"], r["kind"] == "probed")
+            if key in self._deep_term_seen:
+                continue
+            self._deep_term_seen.add(key)
+            if r["n_terminal"] and (best is None or (r["level"], 0.5) < best[:2]):
+                deadlock = dict(level=r["level"], n_states=r["n_states"], n_terminal=r["n_terminal"], n_unsettled=r["n_unsettled"], min_fp=r["min_fp"],
+                                min_index=None, min_fp_unsettled=r["min_fp_unsettled"], min_index_unsettled=None, kernel_ms=r["ms"],
+                                kind_of_level=r["kind"], exact=r["exact"])
+                best = (r["level"], 0.5, None, "deadlock")
+        for r in (self.deep_results() if (deep_state is not None or deep_step is not None) else ()):
             key = (r["level"], r["kind"] == "probed")
             if key in self._deep_seen:
                 continue
@@ -892,6 +912,8 @@ class ModelChecker:
             return None
         if best[2] is not None:
             self.witness = best[2]
+        if best[3] == "deadlock":
+            self.deadlock = deadlock
         return best[3]
 
     def violation_trace(self):
@@ -1019,6 +1041,8 @@ class ModelChecker:
         d = self.deadlock
         if d is None:
             raise ValueError("no terminal state has been found (terminal_scan)")
+        if "kind_of_level" in d:                     # found beyond the record buffers (run(check_deadlock=True, deep=True))
+            return self.deep_terminal_trace(d["level"], probed=d["kind_of_level"] == "probed")
         return self.trace_fp(d["level"], d["min_fp"])
 
     def level_fps(self):
@@ -1191,6 +1215,65 @@ class ModelChecker:
         acts = np.zeros(level + 4, dtype=np.int32)
         n = C.c_uint64()
         check(capi.load().vsrmc_checker_deep_witness(self._h, level, which, k, _p(words), cap_w, _p(off), _p(acts), len(off), C.byref(n)))
+        return [(ACTION_NAMES[acts[t]], words[int(off[t]): int(off[t + 1])].copy()) for t in range(n.value)]
+
+    def deep_terminal_attach(self):
+        """Attach the deadlock check to the search beyond the record buffers (vsrmc_checker_deep_terminal_attach): every deepen() — and every deepen
+        inside advance() / run() / check() — then scans the levels that exist in the seen-set only for terminal states (k_terminal on every scratch
+        slice, each level once) and the probed level as well (k_probe_children writes its states chunk by chunk, k_terminal reads them).  A second call
+        is a no-op.  Results: deep_terminal_results()."""
+        check(capi.load().vsrmc_checker_deep_terminal_attach(self._h))
+
+    def deep_terminal_results(self):
+        """The per-level results of the terminal attachment, ascending by (level, probed) -> [dict(level, kind in DEEP_KINDS, exact, slices, chunks,
+        n_states (kind "probed": the copies scanned), n_terminal, n_unsettled, min_fp, min_fp_unsettled, n_listed, bytes_written, ms, children_ms)];
+        fingerprints None where there is no such state.  kind "probed": distinct states, lower bounds when exact is False."""
+        lib = capi.load()
+        n = C.c_uint64()
+        check(lib.vsrmc_checker_deep_terminal_levels(self._h, None, None, 0, C.byref(n)))
+        lv = np.zeros(max(1, n.value), dtype=np.int32)
+        pr = np.zeros(max(1, n.value), dtype=np.int32)
+        check(lib.vsrmc_checker_deep_terminal_levels(self._h, _p(lv), _p(pr), len(lv), C.byref(n)))
+        none = (1 << 64) - 1
+        out = []
+        for i in range(n.value):
+            d = capi.DeepTerminalInfo()
+            check(lib.vsrmc_checker_deep_terminal_result(self._h, int(lv[i]), int(pr[i]), C.byref(d)))
+            out.append(dict(level=d.level, kind=self.DEEP_KINDS[d.kind], exact=bool(d.exact), slices=int(d.slices), chunks=int(d.chunks), n_states=int(d.n_states),
+                            n_terminal=int(d.n_terminal), n_unsettled=int(d.n_unsettled), min_fp=None if d.min_fp == none else int(d.min_fp),
+                            min_fp_unsettled=None if d.min_fp_unsettled == none else int(d.min_fp_unsettled), n_listed=int(d.n_listed),
+                            bytes_written=int(d.bytes_written), ms=d.ms, children_ms=d.children_ms))
+        return out
+
+    def deep_terminal_states(self, level, probed=False):
+        """The terminal states of a level deep_terminal_results() lists -> (fingerprints ascending, flag bytes: bit 0 set, bit 1 = unsettled); the
+        contract of terminal_states() (VsrmcError -5 when the list overflowed)."""
+        n = C.c_uint64()
+        lib = capi.load()
+        rc = lib.vsrmc_checker_deep_terminal_states(self._h, level, int(probed), None, None, 0, C.byref(n))
+        if rc not in (0, -5):
+            check(rc)
+        fps = np.zeros(max(1, n.value), dtype=np.uint64)
+        flags = np.zeros(max(1, n.value), dtype=np.uint8)
+        check(lib.vsrmc_checker_deep_terminal_states(self._h, level, int(probed), _p(fps), _p(flags), len(fps), C.byref(n)))
+        return fps[: n.value].copy(), flags[: n.value].copy()
+
+    def deep_terminal_trace(self, level=None, probed=False, unsettled=False):
+        """The behaviour from Init into the terminal state (unsettled=True: the unsettled terminal state) with the smallest fingerprint of a level
+        the terminal attachment examined (vsrmc_checker_deep_terminal_witness), the same one in every run: [(action name, record)].  level=None: the
+        deadlock run(check_deadlock=True, deep=True) stopped at."""
+        if level is None:
+            d = self.deadlock
+            if d is None or "kind_of_level" not in d:
+                raise ValueError("run(check_deadlock=True, deep=True) has not stopped at a terminal state beyond the record buffers")
+            level, probed = d["level"], d["kind_of_level"] == "probed"
+        lay = self.model.layout
+        cap_w = (level + 3) * int(lay.max_record_words)
+        words = np.zeros(cap_w, dtype=np.uint64)
+        off = np.zeros(level + 4, dtype=np.uint64)
+        acts = np.zeros(level + 4, dtype=np.int32)
+        n = C.c_uint64()
+        check(capi.load().vsrmc_checker_deep_terminal_witness(self._h, level, int(probed), int(unsettled), _p(words), cap_w, _p(off), _p(acts), len(off), C.byref(n)))
         return [(ACTION_NAMES[acts[t]], words[int(off[t]): int(off[t + 1])].copy()) for t in range(n.value)]
 
     def probe(self):

@@ -15,6 +15,7 @@ struct PassDst {            // where a pass writes (records, refs, fingerprints)
 };
 struct DeepLevelRec { u64 n_new = 0, n_local = 0, generated = 0, max_bag = 0, frontier = 0; };   // n_local: this rank's share (unsharded: all)   // a level that exists in the seen-set only (vsr_deep.hpp)
 struct vsrmc_deep_attach;    // a user's predicates on the levels beyond the record buffers (host_deep_where.hpp)
+struct vsrmc_deep_terminal;  // the deadlock check on the levels beyond the record buffers (host_deep_terminal.hpp)
 struct vsrmc_constraint;     // a user's state constraint, applied to every level right after it is committed (host_constrain.hpp)
 struct vsrmc_action_constraint;   // a user's action constraint: the level step takes the permitted transitions only (host_action_constrain.hpp)
 struct vsrmc_checker {
@@ -125,6 +126,7 @@ struct vsrmc_checker {
   u64 step_total = 0;
   int step_level = -1;
   vsrmc_deep_attach* deep_attach = nullptr;   // vsrmc_checker_deep_attach (host_deep_where.hpp): programs, persistent device buffers, per-level results; not part of a checkpoint
+  vsrmc_deep_terminal* deep_term = nullptr;   // vsrmc_checker_deep_terminal_attach (host_deep_terminal.hpp): persistent device buffers, per-level results; not part of a checkpoint
   u64 table_pruned = 0;                       // states the constraint pruned since the search started: no distinct states, but each keeps its seen-set slot (vsrmc_checker_room)
   vsrmc_constraint* constraint = nullptr;     // vsrmc_checker_constrain_attach (host_constrain.hpp): the program, its device buffers, per-level results; a checkpoint is refused while attached
   vsrmc_action_constraint* action_constraint = nullptr;   // vsrmc_checker_action_constrain_attach (host_action_constrain.hpp): the same for a step program; step_local then runs phase_expand_gated
@@ -146,6 +148,12 @@ void deep_attach_free(vsrmc_checker* c);
 int deep_where_begin(vsrmc_checker* c, int last_level);
 int deep_where_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, int kind, u64 bag, bool probe_next);
 int deep_where_end(vsrmc_checker* c, int rc);
+// host_deep_terminal.hpp (defined there: it needs k_terminal's and k_step_list's host side): the same five for the terminal attachment, called beside them
+void deep_term_restart(vsrmc_checker* c);
+void deep_term_free(vsrmc_checker* c);
+int deep_term_begin(vsrmc_checker* c, int last_level);
+int deep_term_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, int kind, u64 bag, bool probe_next);
+int deep_term_end(vsrmc_checker* c, int rc);
 // host_constrain.hpp (defined there, as above): the filter step_local runs on the level it has just committed; a search that starts over keeps the
 // attachment and evaluates Init again; a checker that is destroyed frees it; 1 while the seen-set holds one level beyond c->level of which every state was pruned
 int constrain_level(vsrmc_checker* c, vsrmc_level_info* info);
@@ -425,6 +433,7 @@ int checker_seed(vsrmc_checker* c) {
   c->probe_viol_key.clear();
   c->probe_viol_level = 0;
   deep_attach_restart(c);
+  deep_term_restart(c);
   c->table_pruned = 0;
   action_constraint_restart(c);
   return constraint_restart(c);                                 // (no constraint attached: nothing)

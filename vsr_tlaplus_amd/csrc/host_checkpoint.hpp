@@ -535,6 +535,7 @@ void vsrmc_checker_destroy(vsrmc_checker* c) {
   if (!c) return;
   (void)hipSetDevice(c->opt.device);
   deep_attach_free(c);
+  deep_term_free(c);
   constraint_free(c);
   action_constraint_free(c);
   if (c->table) (void)hipFree(c->table);

@@ -163,6 +163,7 @@ int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, i
   if (c->level != 1 || c->total_generated != 0 || c->failed || c->deep || c->deep_regen_done)
     return fail(VSRMC_E_STATE, "constraint: attached at level 1 only, to a fresh checker or after vsrmc_checker_reset (Init is subject to it)");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "constraint: predicates are attached for the levels beyond the record buffers (vsrmc_checker_deep_attach): those levels are not constrained");
+  if (c->deep_term) return fail(VSRMC_E_STATE, "constraint: the terminal attachment (vsrmc_checker_deep_terminal_attach) is for the levels beyond the record buffers: those levels are not constrained");
   if (!w) {                                                        // detach: the search starts over unconstrained
     if (!c->constraint) return 0;
     HIPCHK(hipSetDevice(c->opt.device));

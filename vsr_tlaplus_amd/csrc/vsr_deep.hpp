@@ -311,6 +311,7 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
     if (regen) {
       R.ins.materialize_ms += c->expand_ms;                    // time spent regenerating (reported beside the level's own expansion)
       if (c->deep_attach && !R.io && (rc = deep_where_slice(c, B, part, lv + 1, 0, out_bag, false)) != 0) return rc;   // attached predicates: a level is scanned in the first descent that regenerates it
+      if (c->deep_term && !R.io && (rc = deep_term_slice(c, B, part, lv + 1, 0, out_bag, false)) != 0) return rc;      // ... and the terminal attachment's k_terminal, by the same rule
       if (lv + 1 == R.last_regen && !R.insert) rc = R.rebase ? deep_export(R, B, part) : deep_probe(R, B, part, lv + 1, out_bag);
       else rc = deep_descend(R, B.words, B.off, part, out_bag, lv + 1, k + 1);
       if (rc) return rc;
@@ -343,6 +344,7 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
     }
     // attached predicates: the sub-slice of the inserted level, its transitions, and (while the level is clean) its successors = the probed level
     if (c->deep_attach && !R.io && (rc = deep_where_slice(c, B, part, lv + 1, 1, bag_new, R.viol_ins == ~(u64)0)) != 0) return rc;
+    if (c->deep_term && !R.io && (rc = deep_term_slice(c, B, part, lv + 1, 1, bag_new, R.viol_ins == ~(u64)0)) != 0) return rc;   // the terminal attachment: k_terminal on the sub-slice and on its materialised successors
     if (R.viol_ins != ~(u64)0) continue;                       // a violation in the inserted level: it is completed, nothing deeper is probed
     rc = deep_probe(R, B, part, lv + 1, bag_new);
     if (rc) return rc;
@@ -491,9 +493,13 @@ int deep_pass(vsrmc_checker* c, int last_regen, bool insert, vsrmc_level_info* i
   if (rc) { c->failed = 1; return rc; }
   if (io) { u64 sync = 0; rc = io->any(io->ctx, &sync); }      // every rank has cleared its taken bits
   const bool scan = c->deep_attach && !io;
+  const bool tscan = c->deep_term && !io;
   if (!rc && scan) rc = deep_where_begin(c, last_regen + (insert ? 1 : 0));
+  if (!rc && tscan) rc = deep_term_begin(c, last_regen + (insert ? 1 : 0));
   if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 0);
   if (scan) rc = deep_where_end(c, rc);                        // (the inserted level is complete: the probed level's collected copies are resolved against it)
+  if (tscan && insert && !rc) c->deep_lv.back().n_new = R.ins.n_new;   // (unsharded: final; filed again below) the terminal scan checks the inserted level's size too
+  if (tscan) rc = deep_term_end(c, rc);
   if (rc) { c->failed = 1; return rc; }
   const u64 n_local = R.ins.n_new;
   R.ins.viol_fp = R.viol_ins;
@@ -592,8 +598,10 @@ int deep_rebase(vsrmc_checker* c, vsrmc_level_info* out) {
   }
   c->deep_regen_done = true;
   rc = c->deep_attach ? deep_where_begin(c, K) : 0;             // a re-basing descent scans what it regenerates, like any other
+  if (!rc && c->deep_term) rc = deep_term_begin(c, K);
   if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 1);
   if (c->deep_attach) rc = deep_where_end(c, rc);
+  if (c->deep_term) rc = deep_term_end(c, rc);
   if (rc) { c->failed = 1; return rc; }
   u64 cnt[2] = {0, 0};
   u32 xerr = 0;
@@ -676,6 +684,7 @@ int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_lev
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
+  if (c->deep_term) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: the terminal attachment (vsrmc_checker_deep_terminal_attach) scans the passes of vsrmc_checker_deepen / _advance");
   vsrmc_level_info none;
   int rc = vsrmc_checker_deepen(c, virt, probe);
   if (rc || virt->viol_mask || virt->n_new == 0) return rc;
@@ -690,6 +699,7 @@ int32_t vsrmc_checker_probe3(vsrmc_checker* c, vsrmc_level_info* virt1, vsrmc_le
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
+  if (c->deep_term) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: the terminal attachment (vsrmc_checker_deep_terminal_attach) scans the passes of vsrmc_checker_deepen / _advance");
   std::memset(virt2, 0, sizeof(*virt2));
   virt2->viol_fp = virt2->viol_index = ~(u64)0;
   int rc = vsrmc_checker_deepen(c, virt1, probe);

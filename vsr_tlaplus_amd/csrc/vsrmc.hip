@@ -29,6 +29,7 @@
 #include "vsr_step.hpp"
 #include "vsr_action_constrain.hpp"
 #include "vsr_deep_where.hpp"
+#include "vsr_deep_terminal.hpp"
 #include "vsr_sim_where.hpp"
 #include "vsr_sim_constrain.hpp"
 
@@ -130,6 +131,7 @@ extern "C" {
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
 #include "host_action_constrain.hpp"   // action constraints: k_step_list / k_step_apply / k_step_expand in the place of k_expand, per-level figures, permitted traces
 #include "host_deep_where.hpp"   // state / step predicates on the levels beyond the record buffers: attachment, per-level results, witnesses; k_probe_where
+#include "host_deep_terminal.hpp" // the deadlock check on those levels: the terminal attachment, k_terminal per scratch slice, k_probe_children for the probed level
 #include "host_sim_where.hpp"    // simulation with state / step predicates on every walk: k_simulate_where
 #include "host_sim_constrain.hpp" // simulation under a state / an action constraint: k_simulate_constrained
 #include "vsr_bench_layout.hpp"  // measurement: k_expand's staging over records vs over fixed-stride columns (tools/bench_layout.py)

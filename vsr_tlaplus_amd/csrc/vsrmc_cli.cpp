@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -56,6 +57,10 @@ static void usage() {
       "                    every regenerated and inserted level and the transitions out of them, and the state predicates on the probed level too.  Report\n"
       "                    rows follow those lines; -reach / -invariant / -stepReach / -stepInvariant stop there with the messages and exit codes above.\n"
       "                    Per kind of program either the report or the query flags; not with -gpus N > 1, -simulate, -probe2At / -probe3At\n"
+      "  -deepTerminal     with -checkDeadlock and / or -terminalReport (or CHECK_DEADLOCK TRUE in the cfg): terminal states are also looked for on the\n"
+      "                    levels beyond the record buffers (the Virtual / Probe lines) — every regenerated and inserted level, and the probed level, whose\n"
+      "                    states are written out chunk by chunk for the scan.  -checkDeadlock then stops there with the behaviour (exit 11); the report lists\n"
+      "                    those levels.  Combines with -deepPredicates; not with -gpus N > 1, -simulate, -probe2At / -probe3At\n"
       "  -maxDepth N       stop after N BFS levels (Init = level 1)\n"
       "  -device D         HIP device ordinal (default 0)\n"
       "  -gpus N           N > 1: run the sharded checker on N GPUs of this node (re-executes as\n"
@@ -166,17 +171,20 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
+  bool deep_terminal = false;
   bool deep_predicates = false, constrained = false, action_constrained = false, walk_constrained = false, walk_action_constrained = false;
   for (int i = 1; i < argc; i++) {
     if (std::string(argv[i]) == "-walkConstraint") walk_constrained = true;
     if (std::string(argv[i]) == "-walkActionConstraint") walk_action_constrained = true;
     if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
+    if (std::string(argv[i]) == "-deepTerminal") deep_terminal = true;
     if (std::string(argv[i]) == "-constraint") constrained = true;
     if (std::string(argv[i]) == "-actionConstraint") action_constrained = true;
   }
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) {
       if (deep_predicates) { std::fprintf(stderr, "Error: -deepPredicates runs on one GPU: sharded checkers are not scanned (-gpus 1)\n"); return 2; }
+      if (deep_terminal) { std::fprintf(stderr, "Error: -deepTerminal runs on one GPU: sharded checkers are not scanned (-gpus 1)\n"); return 2; }
       if (constrained) { std::fprintf(stderr, "Error: -constraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
       if (action_constrained) { std::fprintf(stderr, "Error: -actionConstraint runs on one GPU: sharded checkers are not constrained (-gpus 1)\n"); return 2; }
       return exec_sharded(argc, argv, i);
@@ -241,6 +249,7 @@ int main(int argc, char** argv) {
     else if (a == "-stepInvariant" && i + 1 < argc) step_invariant_arg = argv[++i];
     else if (a == "-stepReport") step_report = true;
     else if (a == "-deepPredicates") deep_predicates = true;
+    else if (a == "-deepTerminal") deep_terminal = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -288,6 +297,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (deep_terminal) {                                            // refused before any device call
+    const char* why = simulate ? "-deepTerminal belongs to the exhaustive search: -simulate ends a walk at a terminal state by itself"
+                      : (probe2_at > 0 || probe3_at > 0) ? "-deepTerminal cannot be combined with -probe2At / -probe3At"
+                      : (constrained || action_constrained) ? "-deepTerminal cannot be combined with -constraint / -actionConstraint: the levels beyond the record buffers are not constrained"
+                      : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
   vsrmc_model* m = nullptr;
   if (vsrmc_model_load(no_tla || tla.empty() ? nullptr : tla.c_str(), cfg.c_str(), &m) != 0) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
@@ -296,6 +312,10 @@ int main(int argc, char** argv) {
   vsrmc_layout lay;
   vsrmc_model_info(m, &lay);
   if (lay.check_deadlock) check_deadlock = true;
+  if (deep_terminal && !check_deadlock && !terminal_report) {     // (the cfg is a file: still no device call)
+    std::fprintf(stderr, "Error: -deepTerminal needs -checkDeadlock (or CHECK_DEADLOCK TRUE in the cfg) and / or -terminalReport\n");
+    return 2;
+  }
   if (!trace_file.empty()) {   // import of a TLC trace: is it a behaviour of the lowered model?
     std::ifstream f(trace_file, std::ios::binary);
     if (!f) { std::fprintf(stderr, "Error: cannot read %s\n", trace_file.c_str()); return 1; }
@@ -671,6 +691,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  if (deep_terminal && vsrmc_checker_deep_terminal_attach(c) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   if (w_con && vsrmc_checker_constrain_attach(c, w_con, con_index) != 0) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
@@ -780,17 +804,48 @@ int main(int argc, char** argv) {
   uint64_t uns_fp = 0;
   unsigned long long unlisted_levels = 0, unlisted_deadlocks = 0;
   bool scanned_this_step = false;
+  // -deepTerminal: the levels the terminal attachment has examined (level -> its row; a level examined as the probed level and, one pass later, as a scanned
+  // level has ONE row: the scanned one replaces the probed one) and the shallowest terminal state a pass found for -checkDeadlock
+  struct DeepTermRow { int kind, exact; unsigned long long n_states, n_terminal, n_unsettled; uint64_t min_fp, min_fp_unsettled; };
+  std::map<int, DeepTermRow> dterm_rows;
+  std::vector<std::pair<int, int>> dterm_seen;
+  struct DeepDead { int level = 0, probed = 0; unsigned long long n = 0; } deep_dead;
+  auto dterm_scanned = [&](int level) { const auto it = dterm_rows.find(level); return it != dterm_rows.end() && it->second.kind != 2; };
+  static const char* const DTERM_KIND[3] = {"regenerated", "inserted", "probed"};
+  auto dterm_collect = [&]() -> int {                              // the (level, probed) pairs the last pass examined for the first time
+    uint64_t n = 0;
+    if (vsrmc_checker_deep_terminal_levels(c, nullptr, nullptr, 0, &n) != 0) return -1;
+    std::vector<int32_t> lv((size_t)n + 1), pr((size_t)n + 1);
+    if (vsrmc_checker_deep_terminal_levels(c, lv.data(), pr.data(), n, &n) != 0) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+      const std::pair<int, int> key((int)lv[i], (int)pr[i]);
+      if (std::find(dterm_seen.begin(), dterm_seen.end(), key) != dterm_seen.end()) continue;
+      dterm_seen.push_back(key);
+      vsrmc_deep_terminal_info di;
+      if (vsrmc_checker_deep_terminal_result(c, lv[i], pr[i], &di) != 0) return -1;
+      dterm_rows[di.level] = DeepTermRow{di.kind, di.exact, (unsigned long long)di.n_states, (unsigned long long)di.n_terminal, (unsigned long long)di.n_unsettled, di.min_fp, di.min_fp_unsettled};
+      if (json)
+        std::printf("{\"level\": %d, \"stored\": false, \"kind\": \"%s\", \"exact\": %s, \"terminal\": %llu, \"unsettled\": %llu}\n", di.level, DTERM_KIND[di.kind],
+                    di.exact ? "true" : "false", (unsigned long long)di.n_terminal, (unsigned long long)di.n_unsettled);
+      if (di.n_terminal && (!deep_dead.level || di.level < deep_dead.level)) { deep_dead.level = di.level; deep_dead.probed = pr[i]; deep_dead.n = (unsigned long long)di.n_terminal; }
+    }
+    return 0;
+  };
+  std::vector<std::pair<int, unsigned long long>> expanded_unstored;   // (level, deadlocks) of the levels that were expanded from the seen-set alone
+  int bt_probed = -1, bt_unsettled = 0;                            // print_behaviour_to: >= 0 = the behaviour comes from the terminal attachment (1: a probed level)
   auto scan_newest = [&]() -> int {                               // 0, or the error of the scan; a level without records is counted, not listed
     scanned_this_step = false;
     vsrmc_level_info st;
     if (vsrmc_checker_status(c, &st) != 0) return -1;
     if (st.reserved0 != 0 || st.level == last_scanned || st.n_new == 0) return 0;
+    if (deep_terminal && dterm_scanned(st.level)) { last_scanned = st.level; return 0; }   // (scanned by a descent, then re-based onto: reported once)
     const int32_t r = vsrmc_checker_terminal_scan(c, &ti);
     if (r == VSRMC_E_STATE) return 0;
     if (r != 0) return r;
     last_scanned = ti.level;
     levels_scanned++;
     scanned_this_step = true;
+    dterm_rows.erase(ti.level);                                   // (examined earlier as a probed level, stored since — after a re-basing: the stored scan is the level's one row)
     if (ti.n_terminal) term_rows.push_back(TermRow{ti.level, (unsigned long long)ti.n_terminal, (unsigned long long)ti.n_unsettled});
     if (ti.n_unsettled && !uns_level) { uns_level = ti.level; uns_fp = ti.min_fp_unsettled; }
     return 0;
@@ -878,7 +933,8 @@ int main(int argc, char** argv) {
     uint64_t cap_w = ((uint64_t)level + 3) * (uint64_t)lay.max_record_words, n_states = 0;
     std::vector<uint64_t> words(cap_w), off((size_t)level + 3);
     std::vector<int32_t> acts((size_t)level + 3);
-    if (vsrmc_checker_trace_fp(c, level, fp, words.data(), cap_w, off.data(), acts.data(), off.size() - 1, &n_states) != 0) {
+    if ((bt_probed >= 0 ? vsrmc_checker_deep_terminal_witness(c, level, bt_probed, bt_unsettled, words.data(), cap_w, off.data(), acts.data(), off.size() - 1, &n_states)
+                        : vsrmc_checker_trace_fp(c, level, fp, words.data(), cap_w, off.data(), acts.data(), off.size() - 1, &n_states)) != 0) {
       std::printf("Error: %s\n", vsrmc_last_error());
       return false;
     }
@@ -1044,7 +1100,7 @@ int main(int argc, char** argv) {
       if (info.n_new == 0) break;
       depth = info.level;
       rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
-      if (terminal_report && !scanned_this_step) { unlisted_levels++; unlisted_deadlocks += (unsigned long long)info.deadlocks; }   // the level this pass expanded has no records
+      if (terminal_report && !scanned_this_step) expanded_unstored.push_back(std::make_pair(info.level - 1, (unsigned long long)info.deadlocks));   // the level this pass expanded has no records
       if (w_all && !deep_state) where_unexamined++;               // the level this pass inserted is never stored
       if (s_all && !deep_step) step_unexamined++;
       virtual_levels.push_back(info.level);
@@ -1055,7 +1111,11 @@ int main(int argc, char** argv) {
       else
       std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches). (%.2f s)\n", info.level,
                   (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending, dtp);
-      if (info.viol_mask) { probed_violation = true; viol_level = (uint64_t)info.level; break; }
+      // -deepTerminal: what this pass examined.  The shallowest level wins, a built-in violation before a deadlock within a level
+      if (deep_terminal && dterm_collect() != 0) { rc = -1; break; }
+      const bool dead_here = deep_terminal && check_deadlock && deep_dead.level != 0;
+      if (info.viol_mask && !(dead_here && deep_dead.level < info.level)) { probed_violation = true; viol_level = (uint64_t)info.level; break; }
+      if (info.viol_mask) { info.viol_mask = 0; deadlocked = true; break; }
       if (probed.level) {
         if (json)
           std::printf("{\"probed_level\": %d, \"generated\": %llu, \"from\": %llu, \"violating_successors\": %llu, \"seconds\": %.4f}\n", probed.level,
@@ -1063,7 +1123,7 @@ int main(int argc, char** argv) {
         else
         std::printf("Probe(%d): %llu states generated from %llu states, %llu violating successors seen. (%.2f s)\n", probed.level,
                     (unsigned long long)probed.generated, (unsigned long long)probed.frontier, (unsigned long long)probed.pending, dtp);
-        if (probed.viol_mask) {
+        if (probed.viol_mask && !(dead_here && deep_dead.level < probed.level)) {
           probed_violation = true;
           info.viol_mask = probed.viol_mask;
           info.total_generated = probed.total_generated;
@@ -1071,6 +1131,7 @@ int main(int argc, char** argv) {
           break;
         }
       }
+      if (dead_here) { deadlocked = true; break; }
       if (deep_predicates) {
         if (deep_collect() != 0) { rc = -1; break; }
         if (deep_hit.k >= 0) break;
@@ -1251,6 +1312,11 @@ int main(int argc, char** argv) {
     const bool ok = print_behaviour_to(si_query.level, si_query.min_fp[step_hit], false, true, si_query.min_index[step_hit], si_query.min_ordinal[step_hit]);
     if (ok) std::printf("The last step is %s of State %d.\n", vsrmc_action_name(si_query.min_action[step_hit]), si_query.level);
     exit_code = ok ? (inv ? 12 : 0) : 1;
+  } else if (deadlocked && deep_dead.level) {                    // -deepTerminal: found beyond the record buffers, by the terminal attachment
+    std::printf("Error: Deadlock reached (%s%llu state(s) of level %d have no successor).\n", dterm_rows[deep_dead.level].exact ? "" : "at least ", deep_dead.n, deep_dead.level);
+    bt_probed = deep_dead.probed;
+    exit_code = print_behaviour_to(deep_dead.level, dterm_rows[deep_dead.level].min_fp, false) ? 11 : 1;
+    bt_probed = -1;
   } else if (deadlocked && scanned_this_step && ti.n_terminal) {  // found by the scan, before the level was expanded: there is a behaviour to show
     std::printf("Error: Deadlock reached (%llu state(s) of level %d have no successor).\n", (unsigned long long)ti.n_terminal, ti.level);
     exit_code = print_behaviour_to(ti.level, ti.min_fp, false) ? 11 : 1;
@@ -1278,6 +1344,17 @@ int main(int argc, char** argv) {
   }
   if (terminal_report && rc == 0) {
     unsigned long long n_term = 0, n_uns = 0;
+    int dterm_through = 0, dterm_uns_level = 0, dterm_inexact = 0;
+    for (const auto& kv : dterm_rows) {                            // -deepTerminal: the levels beyond the record buffers join the stored ones, in level order
+      levels_scanned++;
+      dterm_through = std::max(dterm_through, kv.first);
+      if (!kv.second.exact) dterm_inexact++;
+      if (kv.second.n_terminal) term_rows.push_back(TermRow{kv.first, kv.second.n_terminal, kv.second.n_unsettled});
+      if (kv.second.n_unsettled && !dterm_uns_level) dterm_uns_level = kv.first;
+    }
+    std::sort(term_rows.begin(), term_rows.end(), [](const TermRow& a, const TermRow& b) { return a.level < b.level; });
+    for (const auto& e : expanded_unstored)
+      if (!dterm_scanned(e.first)) { unlisted_levels++; unlisted_deadlocks += e.second; }
     for (const TermRow& r : term_rows) { n_term += r.n_terminal; n_uns += r.n_unsettled; }
     std::printf("Terminal report: %llu terminal states in %zu of %d scanned levels", n_term, term_rows.size(), levels_scanned);
     if (!term_rows.empty()) {
@@ -1286,12 +1363,27 @@ int main(int argc, char** argv) {
       std::printf(")");
     }
     std::printf(", %llu unsettled (AllReplicasMoveToSameView false).\n", n_uns);
-    if (unlisted_levels)
+    if (unlisted_levels && deep_terminal)
+      std::printf("%llu level(s) were expanded from the seen-set alone before a descent could scan them: %llu terminal states counted, not listed.\n", unlisted_levels, unlisted_deadlocks);
+    else if (unlisted_levels)
       std::printf("%llu level(s) were expanded from the seen-set alone (the parents of the Virtual lines): %llu terminal states counted, not listed.  "
                   "Probed levels are not expanded: their terminal states are neither counted nor listed.\n", unlisted_levels, unlisted_deadlocks);
     if (probe2_at > 0 || probe3_at > 0)
       std::printf("The levels of -probe2At / -probe3At were not scanned: they have no records.\n");
-    if (uns_level) {
+    if (deep_terminal) {
+      if (dterm_inexact) std::printf("%d probed level(s) listed more terminal copies than the list holds: their figures are lower bounds.\n", dterm_inexact);
+      std::printf("Terminal states were examined through level %d (stored levels through %d%s).\n", std::max(last_scanned, dterm_through), last_scanned,
+                  dterm_rows.empty() ? "" : dterm_rows.rbegin()->second.kind == 2 ? "; beyond them by the descents, the last one as the probed level" : "; beyond them by the descents");
+    }
+    if (dterm_uns_level && (!uns_level || dterm_uns_level < uns_level)) {
+      std::printf("A terminal state of level %d has AllReplicasMoveToSameView false: the behaviour below reaches it and stutters there for ever, which is fair under "
+                  "WF_vars(Next) — a counter-example to ViewChangeCompletes.\n", dterm_uns_level);
+      bt_probed = dterm_rows[dterm_uns_level].kind == 2 ? 1 : 0;
+      bt_unsettled = 1;
+      if (!print_behaviour_to(dterm_uns_level, dterm_rows[dterm_uns_level].min_fp_unsettled, true)) exit_code = exit_code ? exit_code : 1;
+      bt_probed = -1;
+      bt_unsettled = 0;
+    } else if (uns_level) {
       std::printf("A terminal state of level %d has AllReplicasMoveToSameView false: the behaviour below reaches it and stutters there for ever, which is fair under "
                   "WF_vars(Next) — a counter-example to ViewChangeCompletes.\n", uns_level);
       if (!print_behaviour_to(uns_level, uns_fp, true)) exit_code = exit_code ? exit_code : 1;
