@@ -384,6 +384,40 @@ int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, i
 int32_t vsrmc_checker_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_constraint_info* out);
 int32_t vsrmc_checker_constraint_pruned(vsrmc_checker* c, uint64_t* fps, uint64_t cap, uint64_t* n);
 
+/* ---- the state constraint on the levels beyond the record buffers (opt-in) -----------------------------------------------
+ * vsrmc_checker_constrain_deep(c, 1): valid on a checker with a state constraint attached and still at level 1 (right after the attachment, or after
+ *   vsrmc_checker_reset, which keeps it).  From then on vsrmc_checker_advance, vsrmc_check, _deepen and _probe do what they do on an unconstrained checker,
+ *   filtered, and the *what = 4 stop does not occur.  on = 0 turns it off again (at level 1).  Without it everything above holds as written.
+ * How: every state of every seen-set-only level sits in a scratch buffer once per descent before anything reads it; k_constrain_slice
+ *   (csrc/vsr_deep_constrain.hpp) runs on every such slice and withdraws the states that fail (off = 0, fp = 0), so that the next nesting level, the probe pass,
+ *   the re-basing export and the inserted level's checksum see in-model states only.  A pruned state keeps its seen-set slot (membership is a function of the
+ *   VIEW): it comes back with every regeneration and is filtered again, with the same verdict.  The figures of a level are recorded once, by the first
+ *   descent that filters it; vsrmc_checker_constraint_info answers for such a level as for a stored one.
+ *   The inserted level of a descent is filtered sub-slice by sub-slice before it is counted: n_new, fp_xor, fp_sum and distinct of its vsrmc_level_info are
+ *   the in-model figures; generated, act_generated and viol_* stay the expand pass's.  The probed level is the successors of its in-model states.
+ *   Two levels reach the seen-set before a record of theirs exists to be judged: the one the first vsrmc_checker_deepen after a stored level inserts, and a
+ *   level adopted after "frontier full".  Their vsrmc_level_info carries the UNFILTERED figures and vsrmc_checker_constraint_deep_info says filtered = 0; the
+ *   next descent regenerates and filters such a level before it expands it, records its figures, and lowers distinct by its pruned count.  No state is
+ *   expanded, probed or exported before it was judged.  A descent whose filtered levels leave nothing to insert ends the search (n_new 0), also when the
+ *   level inserted last turns out wholly out of model one descent later: the depth is then the level below it.
+ * Still refused with the opt-in on (VSRMC_E_STATE): an action constraint (either order of attachment), sharded checkers, exact_ties, vsrmc_checker_probe2 /
+ *   _probe3, _deep_attach, _deep_terminal_attach and _save.
+ * vsrmc_checker_constraint_deep_info: what a level beyond the record buffers adds to its vsrmc_constraint_info.
+ * vsrmc_checker_constraint_pruned_level: vsrmc_checker_constraint_pruned for a level by number — the newest filtered level (0, or its number) or the OTHER
+ *   level the last filtering descent recorded (it records two when it meets a level with filtered = 0); VSRMC_E_ARG for any other level. */
+typedef struct vsrmc_constraint_deep_info {
+  int32_t level;
+  int32_t kind;                                    /* 1: first filtered as a regenerated level, 2: as the inserted level of a descent */
+  int32_t filtered;                                /* 0: complete in the seen-set, not judged yet (kind 1: the next descent does it) */
+  int32_t list_overflowed;                         /* the level pruned more states than its list holds (counts and minima are exact) */
+  uint64_t slices;                                 /* scratch slices the recording descent filtered it in */
+  uint64_t launches;                               /* k_constrain_slice launches on the level, every descent since included */
+  uint64_t regen_records, regen_pruned;            /* records of the level regenerated by every descent so far, and the pruned ones among them */
+} vsrmc_constraint_deep_info;
+int32_t vsrmc_checker_constrain_deep(vsrmc_checker* c, int32_t on);
+int32_t vsrmc_checker_constraint_deep_info(vsrmc_checker* c, int32_t level, vsrmc_constraint_deep_info* out);
+int32_t vsrmc_checker_constraint_pruned_level(vsrmc_checker* c, int32_t level, uint64_t* fps, uint64_t cap, uint64_t* n);
+
 /* ---- action constraints: which steps the search does not take (TLC's ACTION_CONSTRAINT) ---------------------------------
  * One exported predicate P of a step program (vsrmc_step_predicates_compile, below) attached to a checker.  A transition (s, t) by an instance
  * (parent, ordinal) is GENERATED and counted in `generated` and act_generated as ever.  P true: t is fingerprinted and claimed in the seen-set; a new t

@@ -62,6 +62,11 @@ class ConstraintInfo(C.Structure):
                 ("pruned_count", C.c_uint64 * 8), ("pruned_min_fp_k", C.c_uint64 * 8), ("kernel_ms", C.c_double)]
 
 
+class ConstraintDeepInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("kind", C.c_int32), ("filtered", C.c_int32), ("list_overflowed", C.c_int32), ("slices", C.c_uint64),
+                ("launches", C.c_uint64), ("regen_records", C.c_uint64), ("regen_pruned", C.c_uint64)]
+
+
 class ActionConstraintInfo(C.Structure):
     _fields_ = [("level", C.c_int32), ("k", C.c_int32), ("parents", C.c_uint64), ("pairs", C.c_uint64), ("permitted", C.c_uint64), ("blocked", C.c_uint64),
                 ("blocked_act", C.c_uint64 * 16), ("blocked_violating", C.c_uint64), ("blocked_viol_mask", C.c_uint64), ("blocked_min_fp", C.c_uint64),
@@ -180,6 +185,9 @@ SYMBOLS = {
     "vsrmc_checker_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
     "vsrmc_checker_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ConstraintInfo)]),
     "vsrmc_checker_constraint_pruned": (C.c_int32, [V, V, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vsrmc_checker_constrain_deep": (C.c_int32, [V, C.c_int32]),
+    "vsrmc_checker_constraint_deep_info": (C.c_int32, [V, C.c_int32, C.POINTER(ConstraintDeepInfo)]),
+    "vsrmc_checker_constraint_pruned_level": (C.c_int32, [V, C.c_int32, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_checker_action_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
     "vsrmc_checker_action_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ActionConstraintInfo)]),
     "vsrmc_checker_seen_set_load": (C.c_int32, [V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -470,6 +470,7 @@ class ModelChecker:
         self._deep = None                                            # (state Where, step Where) of deep_attach, or None
         self._deep_seen = set()                                      # (level, probed) pairs run(deep=True) has looked at
         self._constraint = None                                      # (Where, k) of constrain(), or None
+        self._constraint_deep = False                                # constrain(.., deep=True): the constraint reaches the levels beyond the record buffers
         self._action_constraint = None                               # (step Where, k) of action_constrain(), or None
         self.stopped = None                                          # the reason advance() gave for ("stopped", ..)
         self._pruned_checked = 0                                     # the newest filtered level run(never=..) has looked at
@@ -527,21 +528,28 @@ class ModelChecker:
 
     def _after_init_filter(self):
         if self._constraint is not None:
+            if self._constraint_deep:                                # (a search that starts over keeps the attachment; the opt-in is asked for again at level 1)
+                check(capi.load().vsrmc_checker_constrain_deep(self._h, 1))
             st = capi.LevelInfo()
             check(capi.load().vsrmc_checker_status(self._h, C.byref(st)))
             self.n_frontier, self.distinct = st.n_new, st.distinct
             self.levels = [dict(level=1, n_new=st.n_new, generated=0, deadlocks=0)]
 
-    def constrain(self, where, name=None):
+    def constrain(self, where, name=None, deep=False):
         """Attach a state constraint (TLC's CONSTRAINT; vsrmc_checker_constrain_attach): the exported predicate `name` (a name or a number; None: the
         program's only one) of the state program `where` (Model.compile_predicates).  A state that fails it is out of model: counted in `generated`,
         checked against the built-in invariants, but no distinct state, never expanded, never a parent in a trace.  At level 1 only (a fresh checker, or
         after reset()); Init is evaluated at once.  where=None detaches and starts over.  While attached, levels are stored only: advance() returns
         ("stopped", ..) and run() "constraint-out-of-room" when the next level does not fit the record buffers; deepen / probe / deep_attach / save
-        are refused."""
+        are refused.
+        deep=True (vsrmc_checker_constrain_deep): the constraint is applied on the levels beyond the record buffers as well — every scratch slice of a
+        descent is filtered before anything reads it (k_constrain_slice) — so advance() / run() / check() / deepen() / probe() go on as on an unconstrained
+        checker, filtered, and run() no longer ends "constraint-out-of-room".  constraint_results() gains rows for those levels, constraint_deep_results()
+        says how each was filtered.  Not with an action constraint, exact_ties, deep_attach / deep_terminal_attach, save."""
         if where is None:
             check(capi.load().vsrmc_checker_constrain_attach(self._h, None, 0))
             self._constraint = None
+            self._constraint_deep = False
             self._fresh()
             return
         if name is None:
@@ -551,6 +559,15 @@ class ModelChecker:
         k = name if isinstance(name, int) else where.names.index(name)
         check(capi.load().vsrmc_checker_constrain_attach(self._h, where._h, k))
         self._constraint = (where, k)
+        self._constraint_deep = False
+        if deep:
+            try:
+                check(capi.load().vsrmc_checker_constrain_deep(self._h, 1))
+            except VsrmcError:
+                capi.load().vsrmc_checker_constrain_attach(self._h, None, 0)     # nothing stays attached by a refused call
+                self._constraint = None
+                raise
+            self._constraint_deep = True
         self._fresh()
         self._after_init_filter()
 
@@ -638,17 +655,43 @@ class ModelChecker:
                 return out
             lv += 1
 
-    def constraint_pruned(self):
+    def constraint_pruned(self, level=None):
         """The pruned states of the newest filtered level -> fingerprints ascending (vsrmc_checker_constraint_pruned).  More than the list holds:
-        VsrmcError (-5) that names the true number; the counts and minima of constraint_results() are exact regardless."""
+        VsrmcError (-5) that names the true number; the counts and minima of constraint_results() are exact regardless.
+        level=L (constrain(.., deep=True)): the list of level L, kept for the levels the last filtering descent recorded — the newest one and, when that
+        descent met a level not judged yet, that level (vsrmc_checker_constraint_pruned_level)."""
         n = C.c_uint64()
         lib = capi.load()
-        rc = lib.vsrmc_checker_constraint_pruned(self._h, None, 0, C.byref(n))
+        lv = 0 if level is None else int(level)
+        rc = lib.vsrmc_checker_constraint_pruned_level(self._h, lv, None, 0, C.byref(n))
         if rc not in (0, -5):
             check(rc)
         fps = np.zeros(max(1, n.value), dtype=np.uint64)
-        check(lib.vsrmc_checker_constraint_pruned(self._h, _p(fps), len(fps), C.byref(n)))
+        check(lib.vsrmc_checker_constraint_pruned_level(self._h, lv, _p(fps), len(fps), C.byref(n)))
         return fps[: n.value].copy()
+
+    def constraint_deep_results(self, level=None):
+        """How the levels beyond the record buffers were filtered (vsrmc_checker_constraint_deep_info; constrain(.., deep=True)) -> [dict(level, kind in
+        ("regenerated", "inserted"), filtered, list_overflowed, slices, launches, regen_records, regen_pruned)], ascending; level=L: that level's dict.
+        filtered False: the level is complete in the seen-set and not judged yet — the next descent regenerates and filters it, and constraint_results()
+        has no row for it until then."""
+        def one(lv):
+            di = capi.ConstraintDeepInfo()
+            check(capi.load().vsrmc_checker_constraint_deep_info(self._h, lv, C.byref(di)))
+            d = {n: int(getattr(di, n)) for n, _ in di._fields_}
+            d["kind"] = {1: "regenerated", 2: "inserted"}[d["kind"]]
+            d["filtered"], d["list_overflowed"] = bool(d["filtered"]), bool(d["list_overflowed"])
+            return d
+        if level is not None:
+            return one(level)
+        out = []
+        for lv in range(2, 512):
+            try:
+                out.append(one(lv))
+            except VsrmcError as e:
+                if e.code != -1:
+                    raise
+        return out
 
     def seed_records(self, words, off):
         """TEST HOOK (the hooks library only: csrc/host_test_seed.hpp): start the search from the wire records words[off[i] : off[i + 1]] instead of
@@ -708,7 +751,8 @@ class ModelChecker:
         self.level, self.n_frontier = st.level, st.n_new
         check(capi.load().vsrmc_checker_options(self._h, C.byref(self.options)))   # (the seen-set may have grown)
         if reason.value == 1:
-            self.violation = dict(level=self._viol_level(d), index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"],
+            beyond = self._constraint_deep and d["level"] > st.level      # found in an inserted or a probed level: that info names its own level
+            self.violation = dict(level=d["level"] if beyond else self._viol_level(d), index=d["viol_index"], fp=d["viol_fp"], mask=d["viol_mask"],
                                   probed=d["viol_index"] == (1 << 64) - 1)
         if reason.value == 5:
             self.stopped = capi.load().vsrmc_last_error().decode()
@@ -870,7 +914,15 @@ class ModelChecker:
         r = self.constraint_results(0)
         if r["level"] <= self._pruned_checked:
             return False
-        self._pruned_checked = r["level"]
+        if self._constraint_deep and self._pruned_checked and r["level"] > self._pruned_checked + 1:
+            # a descent recorded two levels (one that was inserted unfiltered, and the one it inserted): the shallower one first
+            try:
+                below = self.constraint_results(r["level"] - 1)
+                if any(below["pruned_count"][nm] for nm in never.names):
+                    r = below
+            except VsrmcError:
+                pass
+        self._pruned_checked = max(self._pruned_checked, r["level"])
         hits = [nm for nm in never.names if r["pruned_count"][nm]]
         if not hits:
             return False
@@ -919,7 +971,12 @@ class ModelChecker:
     def violation_trace(self):
         """the counter-example of the violation run() / advance() reported, wherever it was found"""
         v = self.violation
-        if self._constraint is not None:             # (the violator may be out of model: its index slot is withdrawn, its seen-set slot is not)
+        if self._constraint_deep and v.get("probed"):    # found beyond the record buffers (an inserted or a probed level): walked from what the pass recorded
+            try:
+                return self.probe_trace()
+            except VsrmcError:                       # (no pass beyond the buffers reported it: an out-of-model violator of a stored level, below)
+                pass
+        if self._constraint is not None:            # (the violator may be out of model: its index slot is withdrawn, its seen-set slot is not)
             return self.trace_fp(v["level"], v["fp"])
         return self.probe_trace() if v.get("probed") else self.trace(v["level"], v["index"])
 

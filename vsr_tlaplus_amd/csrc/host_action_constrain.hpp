@@ -236,6 +236,7 @@ int32_t vsrmc_checker_action_constrain_attach(vsrmc_checker* c, const vsrmc_wher
   }
   if (c->level != 1 || c->total_generated != 0 || c->failed || c->deep || c->deep_regen_done)
     return fail(VSRMC_E_STATE, "action constraint: attached at level 1 only, to a fresh checker or after vsrmc_checker_reset (every transition of the search is subject to it)");
+  if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "action constraint: the state constraint is applied beyond the record buffers (vsrmc_checker_constrain_deep): the transitions there are not judged, an action constraint needs stored levels");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "action constraint: predicates are attached for the levels beyond the record buffers (vsrmc_checker_deep_attach): those levels are not constrained");
   if (c->deep_term) return fail(VSRMC_E_STATE, "action constraint: the terminal attachment (vsrmc_checker_deep_terminal_attach) is for the levels beyond the record buffers: those levels are not constrained");
   if (!w->prog.step) return fail(VSRMC_E_ARG, "action constraint: a state program (vsrmc_where_compile) judges a state; an action constraint is a step predicate (vsrmc_step_predicates_compile: vsrmc_where_desc.step)");

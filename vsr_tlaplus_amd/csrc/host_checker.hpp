@@ -161,6 +161,16 @@ int constraint_restart(vsrmc_checker* c);
 void constraint_free(vsrmc_checker* c);
 int constraint_beyond(const vsrmc_checker* c);
 double constraint_write_ratio(const vsrmc_checker* c);   // states k_expand wrote per state the filter kept, in the newest filtered level (1 without a constraint)
+// host_deep_constrain.hpp (defined there, as above): is the constraint applied beyond the record buffers (vsrmc_checker_constrain_deep)?  Then a descent of
+// the deep search calls: before it starts (the levels first .. last will be filtered), for every scratch slice of a level (inserted != nullptr: the sub-slice
+// of the inserted level — the level's control block comes back), when it is over; then the newest level is dropped if nothing of it is in the model
+bool deep_constrain_on(const vsrmc_checker* c);
+int deep_constrain_filtered_through(const vsrmc_checker* c);
+int deep_constrain_begin(vsrmc_checker* c, int first, int last);
+int deep_constrain_slice(vsrmc_checker* c, const PassDst& B, u64 part, int level, ConstrainCtl* inserted);
+int deep_constrain_end(vsrmc_checker* c, int rc, int base, int last_regen);
+void deep_constrain_drop_empty(vsrmc_checker* c);
+u64 deep_constrain_pruned_of(const vsrmc_checker* c, int level);
 // host_action_constrain.hpp (defined there, as above): phase 1 of a level through the gate, in the place of phase_expand; a search that starts over keeps the
 // attachment and forgets its results; a checker that is destroyed frees it; the behaviour along a walk's fingerprints by permitted steps only
 int phase_expand_gated(vsrmc_checker* c);

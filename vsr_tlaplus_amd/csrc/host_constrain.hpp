@@ -3,6 +3,28 @@
 // pruned states (included by vsrmc.hip: one translation unit, the sections share its anonymous-namespace helpers).
 #pragma once
 
+// what the opt-in for the levels beyond the record buffers adds to an attachment (vsrmc_checker_constrain_deep; host_deep_constrain.hpp)
+struct DeepConstrainLevel {            // one level that was (or still is to be) filtered in a scratch buffer
+  int kind = 0;                        // 1: first filtered as a regenerated level, 2: as the inserted level of a descent
+  bool list_overflowed = false;
+  u64 slices = 0;                      // scratch slices of the descent that recorded its figures
+  u64 launches = 0, regen_records = 0, regen_pruned = 0;   // over every descent since: k_constrain_slice launches; records regenerated, and the pruned ones among them
+};
+struct DeepConstrainState {
+  bool on = false;
+  ConstrainCtl* d_blocks = nullptr;    // one control block per level (index = level), on the device for the whole descent
+  u64* d_list2 = nullptr;              // a second pruned list: a descent records at most two levels (one regenerated for the first time, the inserted one)
+  int filtered_through = 0;            // the deepest level beyond the record buffers whose figures are recorded
+  int first = 0, last = 0;             // the levels of the descent in flight (0: none)
+  int list_level[2] = {0, 0};          // which level appends to d_list / d_list2 in the descent in flight
+  std::vector<DeepConstrainLevel> levels;   // [level]
+  std::vector<u64> count;              // [level]: launches of the descent in flight
+  int other_level = 0;                 // the last recording descent's OTHER level (the regenerated one when it recorded two): its pruned list, ascending
+  std::vector<u64> other_fps;
+  u64 other_total = 0;
+  void restart() { filtered_through = first = last = 0; list_level[0] = list_level[1] = 0; levels.clear(); count.clear(); other_level = 0; other_fps.clear(); other_total = 0; }
+};
+
 struct vsrmc_constraint {
   vsrmc_where prog;                    // a copy: the caller may destroy its own
   int k = 0;                           // the exported predicate that is the constraint
@@ -19,6 +41,7 @@ struct vsrmc_constraint {
   u64 pruned_total = 0;
   int pruned_level = 0;
   int beyond = 0;                      // 1: the last filtered level had no in-model state — it is level c->level + 1 in the seen-set, the search is exhausted
+  DeepConstrainState deep;             // off unless vsrmc_checker_constrain_deep turned it on
 };
 
 namespace {
@@ -131,6 +154,7 @@ int constraint_restart(vsrmc_checker* c) {
   a->write_ratio = 1.0;
   a->pruned_level = 0;
   a->beyond = 0;
+  a->deep.restart();
   return constrain_level(c, nullptr);
 }
 
@@ -150,6 +174,7 @@ void constraint_forget_init(vsrmc_checker* c) {
   a->write_ratio = 1.0;
   a->pruned_level = 0;
   a->beyond = 0;
+  a->deep.restart();
 }
 #endif
 

@@ -12,7 +12,7 @@ int32_t vsrmc_checker_probe(vsrmc_checker* c, vsrmc_level_info* info) {
   // sharded: the rank probes its part of the newest level against ITS part of the seen-set; the violating successors it could
   // not find there (vsrmc_checker_probe_candidates) still have to be shown to their owners (sharded.py: ShardedChecker.probe)
   if (c->opt.exact_ties) return fail(VSRMC_E_STATE, "probe levels need a single-pass checker");
-  if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->constraint && !deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->failed && c->failed_code != ERR_FRONTIER_FULL) return fail(VSRMC_E_STATE, "the checker stopped on an error");
   c->failed = 0;
@@ -371,7 +371,7 @@ int32_t vsrmc_checker_advance(vsrmc_checker* c, vsrmc_level_info* a, vsrmc_level
   std::memset(b, 0, sizeof(*b));
   b->viol_fp = b->viol_index = ~(u64)0;
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "sharded checker: vsrmc_shard_loop_advance");
-  if (c->constraint || c->action_constraint) {                   // levels are stored, or the run ends: no deep pass runs over a half-filtered search
+  if ((c->constraint && !deep_constrain_on(c)) || c->action_constraint) {   // levels are stored, or the run ends (vsrmc_checker_constrain_deep lifts that for a state constraint): no deep pass runs over a half-filtered search
     auto no_room = [&](const char* why) {
       *what = 4;
       std::memset(a, 0, sizeof(*a));

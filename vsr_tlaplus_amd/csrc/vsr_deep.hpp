@@ -287,11 +287,13 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
   sl.cap_n = B.cap; sl.cap_w = B.words_cap; sl.g1 = std::max<u64>(1, c->deep_g); sl.stride = (u64)c->lds_stride;
   sl.cap_c = deep_cand_bound(R, sl.g1);
   const bool regen = lv + 1 <= R.last_regen;
+  const bool filter = !R.io && deep_constrain_on(c);             // the state constraint reaches these levels (host_deep_constrain.hpp): every slice is filtered before anything reads it
   const DeepLevel& next = c->deep_lv[(size_t)(lv - R.base)];   // level lv + 1
   if (regen) {
     // MODE_REGEN writes a state where its min-key parent sits — keys order by the parent's fingerprint, so the states of the next level
     // spread evenly over the parents: (states of level lv+1 per valid parent, known exactly) x (a record of the source + 2 words)
-    const u64 parents = lv == R.base ? c->n_valid : c->deep_lv[(size_t)(lv - R.base - 1)].n_local;   // (a rank regenerates about what it inserted)
+    const DeepLevel& here = c->deep_lv[(size_t)(lv == R.base ? 0 : lv - R.base - 1)];
+    const u64 parents = lv == R.base ? c->n_valid : filter ? here.n_new : here.n_local;   // (a rank regenerates about what it inserted; under a constraint only the in-model states are parents)
     const double per_n = (double)next.n_local / (double)std::max<u64>(1, parents);
     const double wbar = (lv == R.base ? (double)c->cur_w / (double)std::max<u64>(1, c->n_valid) : (double)(M.fixed + (int)src_bag)) + 2.0;
     sl.expect(per_n, per_n * wbar);
@@ -310,6 +312,7 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
     sl.observe(n, part, c->h.words_new);
     if (regen) {
       R.ins.materialize_ms += c->expand_ms;                    // time spent regenerating (reported beside the level's own expansion)
+      if (filter && (rc = deep_constrain_slice(c, B, part, lv + 1, nullptr)) != 0) return rc;   // the pruned states came back with the regeneration: withdrawn again, no host round trip
       if (c->deep_attach && !R.io && (rc = deep_where_slice(c, B, part, lv + 1, 0, out_bag, false)) != 0) return rc;   // attached predicates: a level is scanned in the first descent that regenerates it
       if (c->deep_term && !R.io && (rc = deep_term_slice(c, B, part, lv + 1, 0, out_bag, false)) != 0) return rc;      // ... and the terminal attachment's k_terminal, by the same rule
       if (lv + 1 == R.last_regen && !R.insert) rc = R.rebase ? deep_export(R, B, part) : deep_probe(R, B, part, lv + 1, out_bag);
@@ -327,7 +330,13 @@ int deep_descend(DeepRun& R, const u64* src_words, const u64* src_off, u64 n_idx
     }
     if (!part) continue;
     const u64 bag_new = std::min<u64>(c->h.max_bag, (u64)M.max_bag);
-    {   // checksums of the level: the sub-slice's fingerprints sit in the scratch buffer until it is reused
+    if (filter) {   // the constraint first: its kept xor / sum / count ARE the checksum of what stays of the level (one pass over the sub-slice instead of two)
+      ConstrainCtl hb;
+      if ((rc = deep_constrain_slice(c, B, part, lv + 1, &hb)) != 0) return rc;
+      R.ins.fp_xor = hb.kept_xor;                                // (the level's block accumulates over its sub-slices)
+      R.ins.fp_sum = hb.kept_sum;
+      R.ins.n_new = hb.kept;
+    } else {   // checksums of the level: the sub-slice's fingerprints sit in the scratch buffer until it is reused
       u64 hsum[3] = {0, 0, 0};
       bool ok = hipMemsetAsync(R.d_sum, 0, 24, c->stream) == hipSuccess;
       if (ok) hipLaunchKernelGGL(k_level_checksum, dim3(1024), dim3(256), 0, c->stream, B.fp, part, R.d_sum);
@@ -496,12 +505,15 @@ int deep_pass(vsrmc_checker* c, int last_regen, bool insert, vsrmc_level_info* i
   const bool tscan = c->deep_term && !io;
   if (!rc && scan) rc = deep_where_begin(c, last_regen + (insert ? 1 : 0));
   if (!rc && tscan) rc = deep_term_begin(c, last_regen + (insert ? 1 : 0));
+  const bool filter = !io && deep_constrain_on(c);
+  if (!rc && filter) rc = deep_constrain_begin(c, c->level + 1, last_regen + (insert ? 1 : 0));
   if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 0);
+  if (filter) rc = deep_constrain_end(c, rc, c->level, last_regen);   // the figures of the levels filtered for the first time; a level that was inserted unfiltered is corrected
   if (scan) rc = deep_where_end(c, rc);                        // (the inserted level is complete: the probed level's collected copies are resolved against it)
   if (tscan && insert && !rc) c->deep_lv.back().n_new = R.ins.n_new;   // (unsharded: final; filed again below) the terminal scan checks the inserted level's size too
   if (tscan) rc = deep_term_end(c, rc);
   if (rc) { c->failed = 1; return rc; }
-  const u64 n_local = R.ins.n_new;
+  const u64 n_local = R.ins.n_new + (filter && insert ? deep_constrain_pruned_of(c, last_regen + 1) : 0);   // what a descent regenerates of the level: kept + pruned
   R.ins.viol_fp = R.viol_ins;
   R.ins.viol_mask = (int32_t)R.mask_ins;
   R.prb.viol_mask = (int32_t)R.mask_prb;
@@ -526,6 +538,10 @@ int deep_pass(vsrmc_checker* c, int last_regen, bool insert, vsrmc_level_info* i
     ins->seconds = dt * ((R.ins.expand_ms + R.ins.materialize_ms) / std::max(1e-9, ms_all));   // the levels share the pass: split by kernel time
     if (R.ins.n_new) c->deep = last_regen + 1 - c->level;        // an empty level is no level: the search is exhausted at the one below
     else c->deep_lv.pop_back();
+    if (filter) {
+      deep_constrain_drop_empty(c);                              // the level below turned out wholly out of model in this descent: no level either
+      if (!R.ins.n_new) ins->level = c->level + c->deep;
+    }
     if (ins->viol_fp != ~(u64)0) {
       c->probe_fp = ins->viol_fp;
       c->probe_level = last_regen + 1;
@@ -562,6 +578,7 @@ bool rebase_pays(const vsrmc_checker* c) {
   if (!c->deep || c->failed || c->opt.world > 1 || c->opt.exact_ties || c->rebase_off) return false;
   const DeepLevel& top = c->deep_lv.back();
   if (top.n_new == 0) return false;
+  if (deep_constrain_on(c) && c->level + c->deep > deep_constrain_filtered_through(c)) return false;   // (not judged yet: its in-model size is not known; the next descent filters it)
   if (!(c->deep >= 2 || top.n_new <= c->n_valid)) return false;           // (a level that did not fit a moment ago: wait until the run has shown where it goes)
   const Model& M = c->model.M;
   const int nxt = c->cur ^ 1;
@@ -599,7 +616,10 @@ int deep_rebase(vsrmc_checker* c, vsrmc_level_info* out) {
   c->deep_regen_done = true;
   rc = c->deep_attach ? deep_where_begin(c, K) : 0;             // a re-basing descent scans what it regenerates, like any other
   if (!rc && c->deep_term) rc = deep_term_begin(c, K);
+  const bool filter = deep_constrain_on(c);                       // the new base is packed from filtered slices
+  if (!rc && filter) rc = deep_constrain_begin(c, c->level + 1, K);
   if (!rc) rc = deep_descend(R, c->words[c->cur], c->off[c->cur], c->n_frontier, c->bag_known ? c->cur_max_bag : (u64)M.max_bag, c->level, 1);
+  if (filter) rc = deep_constrain_end(c, rc, c->level, K);
   if (c->deep_attach) rc = deep_where_end(c, rc);
   if (c->deep_term) rc = deep_term_end(c, rc);
   if (rc) { c->failed = 1; return rc; }
@@ -658,7 +678,7 @@ extern "C" {
 // (vsrmc_checker_probe_trace reconstructs the counter-example); inserted->n_new == 0: the search is exhausted.
 int32_t vsrmc_checker_deepen(vsrmc_checker* c, vsrmc_level_info* inserted, vsrmc_level_info* probed) {
   if (!c || !inserted || !probed) return fail(VSRMC_E_ARG, "NULL argument");
-  if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->constraint && !deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   int rc = deep_check_ready(c, 2, false);
   if (rc) return rc;
@@ -681,6 +701,7 @@ int32_t vsrmc_checker_deepen(vsrmc_checker* c, vsrmc_level_info* inserted, vsrmc
 int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_level_info* probe) {
   if (!c || !virt || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2 starts from a materialised level");
+  if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: the constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance only (vsrmc_checker_constrain_deep): this path does not filter");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
@@ -696,6 +717,7 @@ int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_lev
 int32_t vsrmc_checker_probe3(vsrmc_checker* c, vsrmc_level_info* virt1, vsrmc_level_info* virt2, vsrmc_level_info* probe) {
   if (!c || !virt1 || !virt2 || !probe) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3 starts from a materialised level");
+  if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: the constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance only (vsrmc_checker_constrain_deep): this path does not filter");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");

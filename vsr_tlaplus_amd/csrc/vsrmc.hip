@@ -25,6 +25,7 @@
 #include "vsr_terminal.hpp"
 #include "vsr_where.hpp"
 #include "vsr_constrain.hpp"
+#include "vsr_deep_constrain.hpp"
 #include "vsr_where_parse.hpp"
 #include "vsr_step.hpp"
 #include "vsr_action_constrain.hpp"
@@ -127,6 +128,7 @@ extern "C" {
 #include "host_terminal.hpp"     // terminal states: k_terminal over a batch / the newest stored level
 #include "host_where.hpp"        // state predicates: compile, k_where over a batch / the newest stored level
 #include "host_constrain.hpp"    // state constraints: k_constrain over every level right after it is committed, per-level figures, the pruned list
+#include "host_deep_constrain.hpp" // ... and on the levels beyond the record buffers (opt-in): k_constrain_slice per scratch slice of a descent, per-level control blocks
 #include "host_step_slices.hpp"  // the slice driver of k_step_list (step_slices) over the slice policy (host_slice_policy.hpp)
 #include "host_step.hpp"         // step predicates: compile, k_step_list / k_step_apply over a batch / the newest stored level
 #include "host_action_constrain.hpp"   // action constraints: k_step_list / k_step_apply / k_step_expand in the place of k_expand, per-level figures, permitted traces

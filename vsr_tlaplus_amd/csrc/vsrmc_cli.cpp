@@ -115,6 +115,11 @@ static void usage() {
       "                    are stored only: when the next one does not fit the record buffers the run ends, incomplete (exit 4).  -invariant NAMES are checked\n"
       "                    on the states the constraint prunes as well.  Not with -gpus N > 1, -simulate, -deepPredicates, -probeLast, -probe2At, -probe3At,\n"
       "                    -checkpoint, -recover, -audit.  With -json the level lines carry \"kept\" and \"pruned\"\n"
+      "  -deepConstraint   with -constraint NAME: the constraint is applied on the levels beyond the record buffers as well (every scratch slice of a descent is\n"
+      "                    filtered before anything reads it), so the run goes on past them instead of ending with exit 4.  The Virtual lines then carry the\n"
+      "                    in-model figures; a level that reached the seen-set before its records could be judged is marked so and gets a Filtered(L) line\n"
+      "                    from the next pass; the closing line gives the kept and pruned totals.  -probeLast is allowed; not with -actionConstraint,\n"
+      "                    -deepPredicates, -deepTerminal, -probe2At, -probe3At, -checkpoint, -recover, -audit, -gpus N > 1\n"
       "  -actionConstraint NAME  with -steps FILE: the exported step predicate NAME is an action constraint (TLC's ACTION_CONSTRAINT): a transition that\n"
       "                    fails it is generated and counted but not taken; its successor may still be reached through a permitted transition.  Init is not\n"
       "                    subject to it; every behaviour printed takes permitted steps only.  Combines with -constraint, -invariant, -reach, -stepInvariant,\n"
@@ -171,7 +176,7 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
-  bool deep_terminal = false;
+  bool deep_terminal = false, deep_constraint = false;
   bool deep_predicates = false, constrained = false, action_constrained = false, walk_constrained = false, walk_action_constrained = false;
   for (int i = 1; i < argc; i++) {
     if (std::string(argv[i]) == "-walkConstraint") walk_constrained = true;
@@ -179,6 +184,7 @@ int main(int argc, char** argv) {
     if (std::string(argv[i]) == "-deepPredicates") deep_predicates = true;
     if (std::string(argv[i]) == "-deepTerminal") deep_terminal = true;
     if (std::string(argv[i]) == "-constraint") constrained = true;
+    if (std::string(argv[i]) == "-deepConstraint") deep_constraint = true;
     if (std::string(argv[i]) == "-actionConstraint") action_constrained = true;
   }
   for (int i = 1; i + 1 < argc; i++)
@@ -250,17 +256,26 @@ int main(int argc, char** argv) {
     else if (a == "-stepReport") step_report = true;
     else if (a == "-deepPredicates") deep_predicates = true;
     else if (a == "-deepTerminal") deep_terminal = true;
+    else if (a == "-deepConstraint") deep_constraint = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
   }
   if (cfg.empty()) { usage(); return 2; }
+  if (deep_constraint) {                                          // refused before any device call
+    const char* why = !constrained ? "-deepConstraint needs -constraint NAME: it is that constraint which is applied beyond the record buffers"
+                      : action_constrained ? "-deepConstraint cannot be combined with -actionConstraint: beyond the record buffers the transitions are not judged, only a state constraint is applied there"
+                      : deep_predicates ? "-deepConstraint cannot be combined with -deepPredicates: the probed level's successors are judged on arrival, which the attached scans do not know about"
+                      : deep_terminal ? "-deepConstraint cannot be combined with -deepTerminal: the probed level's successors are judged on arrival, which the terminal attachment does not know about"
+                      : (probe2_at > 0 || probe3_at > 0) ? "-deepConstraint cannot be combined with -probe2At / -probe3At: those passes do not filter" : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
   if (constrained) {                                              // refused before any device call
     const char* why = constraint_arg.empty() ? "-constraint needs a NAME"
                       : predicates_file.empty() ? "-constraint NAME needs -predicates FILE"
                       : simulate ? "-constraint belongs to the exhaustive search: a random walk (-simulate) is not constrained: use -walkConstraint NAME"
                       : deep_predicates ? "-constraint cannot be combined with -deepPredicates: the levels beyond the record buffers are not constrained"
-                      : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-constraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
+                      : ((probe_last && !deep_constraint) || probe2_at > 0 || probe3_at > 0) ? "-constraint cannot be combined with -probeLast / -probe2At / -probe3At: the levels beyond the record buffers are not constrained"
                       : (!chk_file.empty() || !recover_file.empty()) ? "-constraint cannot be combined with -checkpoint / -recover: a checkpoint does not name the constraint"
                       : audit ? "-constraint cannot be combined with -audit" : nullptr;
     if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
@@ -699,6 +714,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  if (w_con && deep_constraint && vsrmc_checker_constrain_deep(c, 1) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   if (s_act && vsrmc_checker_action_constrain_attach(c, s_act, 0) != 0) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
@@ -771,6 +790,27 @@ int main(int argc, char** argv) {
     return true;
   };
   con_collect();                                                  // (Init)
+  // -deepConstraint: a pass beyond the record buffers records up to two levels (one that was inserted before it could be judged, and the one it inserted)
+  unsigned long long con_kept_deep = 0, con_pruned_deep = 0;
+  int con_deep_levels = 0;
+  auto con_collect_deep = [&](int inserted_level) {
+    vsrmc_constraint_info newest;
+    if (!w_con || vsrmc_checker_constraint_info(c, 0, &newest) != 0) return;
+    for (int lvl = con_seen_level + 1; lvl <= newest.level; lvl++) {
+      vsrmc_constraint_info ci;
+      if (vsrmc_checker_constraint_info(c, lvl, &ci) != 0) continue;
+      con_seen_level = lvl;
+      con_pruned_total += (unsigned long long)ci.pruned;
+      con_kept_deep += (unsigned long long)ci.kept;
+      con_pruned_deep += (unsigned long long)ci.pruned;
+      con_deep_levels++;
+      for (size_t k = 0; k < con_inv_names.size() && con_hit < 0; k++)
+        if (ci.pruned_count[k]) { con_hit = (int)k; con_hit_level = ci.level; con_hit_fp = ci.pruned_min_fp_k[k]; }
+      if (lvl == inserted_level) con_info = ci;
+      else if (json) std::printf("{\"filtered_level\": %d, \"kept\": %llu, \"pruned\": %llu}\n", lvl, (unsigned long long)ci.kept, (unsigned long long)ci.pruned);
+      else std::printf("Filtered(%d): %llu in the model, %llu out of model (regenerated and judged before it was expanded).\n", lvl, (unsigned long long)ci.kept, (unsigned long long)ci.pruned);
+    }
+  };
   // -actionConstraint: the figures of every step taken under it, the run's totals
   unsigned long long act_blocked_total = 0, act_blocked_by[16] = {0}, act_blocked_violating = 0;
   int act_seen_level = 0;
@@ -1097,17 +1137,31 @@ int main(int argc, char** argv) {
       for (int a2 = 1; a2 < 16; a2++) cov[a2] += info.act_generated[a2];
       const double dtp = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       if (dump) { std::printf("Level %d is not stored (it does not fit the record buffers): -dump ends at level %d.\n", info.level, depth); std::fclose(dump); dump = nullptr; }
-      if (info.n_new == 0) break;
-      depth = info.level;
-      rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
+      con_info.level = 0;
+      if (deep_constraint) con_collect_deep(info.n_new ? info.level : info.level + 1);   // (first: a level that was inserted unfiltered gets its Filtered line before the Virtual line of the level above it)
+      if (info.n_new == 0 && !info.viol_mask) break;
+      if (info.n_new) depth = info.level;
+      if (info.n_new) rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
       if (terminal_report && !scanned_this_step) expanded_unstored.push_back(std::make_pair(info.level - 1, (unsigned long long)info.deadlocks));   // the level this pass expanded has no records
       if (w_all && !deep_state) where_unexamined++;               // the level this pass inserted is never stored
       if (s_all && !deep_step) step_unexamined++;
       virtual_levels.push_back(info.level);
-      if (json)
+      if (json && deep_constraint)                                  // "filtered": false = the unfiltered figures of a level the next pass judges
+        std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"filtered\": %s, \"kept\": %llu, "
+                    "\"pruned\": %llu, \"seconds\": %.4f}\n", info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
+                    (unsigned long long)info.deadlocks, (unsigned long long)info.pending, con_info.level == info.level ? "true" : "false",
+                    con_info.level == info.level ? (unsigned long long)con_info.kept : 0ull, con_info.level == info.level ? (unsigned long long)con_info.pruned : 0ull, dtp);
+      else if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
                     (unsigned long long)info.deadlocks, (unsigned long long)info.pending, dtp);
+      else if (deep_constraint && con_info.level == info.level)     // filtered sub-slice by sub-slice before it was counted: the in-model figures
+      std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches); %llu in the model, %llu out of model. (%.2f s)\n", info.level,
+                  (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending,
+                  (unsigned long long)con_info.kept, (unsigned long long)con_info.pruned, dtp);
+      else if (deep_constraint)
+      std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches); not judged yet: the next pass filters it. (%.2f s)\n", info.level,
+                  (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending, dtp);
       else
       std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches). (%.2f s)\n", info.level,
                   (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending, dtp);
@@ -1132,6 +1186,8 @@ int main(int argc, char** argv) {
         }
       }
       if (dead_here) { deadlocked = true; break; }
+      if (con_hit >= 0) break;                                    // -invariant fails among the states this pass pruned
+      if (info.n_new == 0) break;
       if (deep_predicates) {
         if (deep_collect() != 0) { rc = -1; break; }
         if (deep_hit.k >= 0) break;
@@ -1335,6 +1391,9 @@ int main(int argc, char** argv) {
   }
   if (w_con && rc == 0)
     std::printf("CONSTRAINT %s: %llu states were out of model and not explored; the distinct states below are the in-model ones.\n", constraint_arg.c_str(), con_pruned_total);
+  if (w_con && deep_constraint && rc == 0)
+    std::printf("CONSTRAINT %s, levels beyond the record buffers included: %llu in-model states kept and %llu pruned in the %d level(s) filtered there.\n", constraint_arg.c_str(),
+                con_kept_deep, con_pruned_deep, con_deep_levels);
   if (s_act && rc == 0) {
     std::string per;
     for (int a2 = 0; a2 < 16; a2++)
