@@ -443,7 +443,8 @@ int32_t vsrmc_checker_constraint_pruned_level(vsrmc_checker* c, int32_t level, u
  *   does not export, and a program that reads aux_svc or aux_client_acked, primed or not (outside VIEW: the copy of a state that arrived first would decide
  *   which transitions are taken; under SYMMETRY the compiler already refuses value literals); VSRMC_E_STATE with exact_ties = 1, on a sharded checker
  *   (world > 1), after level 1, with predicates attached by vsrmc_checker_deep_attach, and for a second attachment.
- * While attached: vsrmc_checker_deepen, _probe, _probe2, _probe3, _deep_attach and _save are refused (VSRMC_E_STATE), and vsrmc_checker_advance stores
+ * While attached (and unless vsrmc_checker_action_constrain_deep, below, lifts it for _deepen, _probe and _advance): vsrmc_checker_deepen, _probe, _probe2,
+ *   _probe3, _deep_attach and _save are refused (VSRMC_E_STATE), and vsrmc_checker_advance stores
  *   levels only — when the next level is not predicted to fit, or overflowed, it returns 0 with *what = 4 (vsrmc_check: stop_reason 5), as with a state
  *   constraint.  Blocked successors take neither record room nor a seen-set slot: the prediction is not scaled for them and vsrmc_checker_room counts the
  *   distinct states as the table's load.
@@ -464,6 +465,40 @@ typedef struct vsrmc_action_constraint_info {
 } vsrmc_action_constraint_info;
 int32_t vsrmc_checker_action_constrain_attach(vsrmc_checker* c, const vsrmc_where* step_program, int32_t name_index);
 int32_t vsrmc_checker_action_constraint_info(vsrmc_checker* c, int32_t level, vsrmc_action_constraint_info* out);
+/* ---- an action constraint on the levels beyond the record buffers (opt-in) -----------------------------------------------
+ * vsrmc_checker_action_constrain_deep(c, 1): called on a checker with an action constraint attached and still at level 1 (right after the attachment, or
+ *   after vsrmc_checker_reset), like vsrmc_checker_constrain_deep.  From then on vsrmc_checker_advance, vsrmc_check, vsrmc_checker_deepen and
+ *   vsrmc_checker_probe go on past the record buffers as on an unconstrained checker, taking PERMITTED transitions only — *what = 4 no longer occurs, and a
+ *   stored level that overflowed is adopted as the first seen-set-only level.  (c, 0) turns it off again, at level 1.  Without the call every answer is what
+ *   it was.
+ * The semantics are those above, carried over: a blocked transition is generated and counted and not taken — its successor is not fingerprinted into the
+ *   seen-set by that edge, not written and not probed; the same state may enter through a permitted edge of the same or a later level.  Every parent pointer
+ *   in the seen-set was written by a permitted transition, so vsrmc_checker_trace_fp on a fingerprint of a deep level and vsrmc_checker_probe_trace (its last
+ *   step into a violator of the probed level included) take permitted steps only.  On the probed level only successors of permitted transitions are
+ *   candidates for a violation.  A blocked successor's invariants are evaluated only to count it.  Two successors of one level with one VIEW fingerprint and
+ *   different aux keys fail the run with the stored path's message.
+ * How: the record-less first pass, the level a descent inserts and the probed level run k_step_list, k_step_apply and k_step_expand (its insert, stored and
+ *   probe modes: csrc/vsr_action_constrain.hpp) over slices of their parents in the place of k_expand; the regenerating passes run k_expand unchanged — a
+ *   regenerating lane takes a state only under the key a permitted transition wrote, so the regenerated level is the recorded one (§9m).  No claim bitmap is
+ *   kept: regeneration asks the seen-set.
+ * Refused with the opt-in on (VSRMC_E_STATE): beside a state constraint, deep or not (the record-less pass cannot judge states — the combination is the
+ *   follow-up), and vsrmc_checker_constrain_deep / _constrain_attach after it; vsrmc_checker_deep_attach, _deep_terminal_attach, _probe2, _probe3, _save;
+ *   exact_ties and sharded checkers refuse the attachment already.
+ * vsrmc_checker_action_constraint_deep_info: the figures of the gated passes that led INTO `level`, a level beyond the record buffers: kind 1 = inserted
+ *   record-less (the first pass, or a stored level that overflowed and was adopted), 2 = inserted by a descent, 3 = probed (the level after the inserted
+ *   one: nothing of it is in the seen-set; the next pass inserts it and files it anew as kind 2).  VSRMC_E_ARG for any other level. */
+typedef struct vsrmc_action_constraint_deep_info {
+  int32_t level, kind;
+  uint64_t parents;                                /* states expanded (a probed level after a violation in the inserted one: fewer than the level has) */
+  uint64_t pairs, permitted, blocked;              /* transitions generated = taken (kind 3: looked up) + not taken */
+  uint64_t blocked_act[16];                        /* blocked per action id */
+  uint64_t blocked_violating, blocked_viol_mask;   /* as in vsrmc_action_constraint_info */
+  uint64_t blocked_min_fp, blocked_viol_min_fp;    /* the smallest PARENT fingerprint of a blocked pair / of one whose successor fails an invariant; ~0 if none */
+  uint64_t slices, relisted, launches;             /* k_step_list launches over all the gated passes into the level; the void ones among them; kernel launches in all */
+  double list_ms, verdict_ms, expand_ms;           /* HIP-event time of k_step_list, k_step_apply, k_step_expand, summed */
+} vsrmc_action_constraint_deep_info;
+int32_t vsrmc_checker_action_constrain_deep(vsrmc_checker* c, int32_t on);
+int32_t vsrmc_checker_action_constraint_deep_info(vsrmc_checker* c, int32_t level, vsrmc_action_constraint_deep_info* out);
 /* the seen-set's load as the table shows it: slots that hold a fingerprint, of how many.  Counted on the host from a copy of the table (tests, reports). */
 int32_t vsrmc_checker_seen_set_load(vsrmc_checker* c, uint64_t* occupied, uint64_t* slots);
 

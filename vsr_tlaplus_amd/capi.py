@@ -74,6 +74,13 @@ class ActionConstraintInfo(C.Structure):
                 ("list_ms", C.c_double), ("verdict_ms", C.c_double), ("expand_ms", C.c_double)]
 
 
+class ActionConstraintDeepInfo(C.Structure):
+    _fields_ = [("level", C.c_int32), ("kind", C.c_int32), ("parents", C.c_uint64), ("pairs", C.c_uint64), ("permitted", C.c_uint64), ("blocked", C.c_uint64),
+                ("blocked_act", C.c_uint64 * 16), ("blocked_violating", C.c_uint64), ("blocked_viol_mask", C.c_uint64), ("blocked_min_fp", C.c_uint64),
+                ("blocked_viol_min_fp", C.c_uint64), ("slices", C.c_uint64), ("relisted", C.c_uint64), ("launches", C.c_uint64),
+                ("list_ms", C.c_double), ("verdict_ms", C.c_double), ("expand_ms", C.c_double)]
+
+
 class StepInfo(C.Structure):
     _fields_ = [("level", C.c_int32), ("reserved0", C.c_int32), ("n_states", C.c_uint64), ("n_pairs", C.c_uint64), ("n_err", C.c_uint64),
                 ("count", C.c_uint64 * 8), ("min_fp", C.c_uint64 * 8), ("min_index", C.c_uint64 * 8), ("min_ordinal", C.c_uint32 * 8),
@@ -190,6 +197,8 @@ SYMBOLS = {
     "vsrmc_checker_constraint_pruned_level": (C.c_int32, [V, C.c_int32, V, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vsrmc_checker_action_constrain_attach": (C.c_int32, [V, V, C.c_int32]),
     "vsrmc_checker_action_constraint_info": (C.c_int32, [V, C.c_int32, C.POINTER(ActionConstraintInfo)]),
+    "vsrmc_checker_action_constrain_deep": (C.c_int32, [V, C.c_int32]),
+    "vsrmc_checker_action_constraint_deep_info": (C.c_int32, [V, C.c_int32, C.POINTER(ActionConstraintDeepInfo)]),
     "vsrmc_checker_seen_set_load": (C.c_int32, [V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vsrmc_step_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),
     "vsrmc_step_predicates_compile": (C.c_int32, [V, C.c_char_p, C.POINTER(V)]),

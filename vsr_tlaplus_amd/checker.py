@@ -472,6 +472,7 @@ class ModelChecker:
         self._constraint = None                                      # (Where, k) of constrain(), or None
         self._constraint_deep = False                                # constrain(.., deep=True): the constraint reaches the levels beyond the record buffers
         self._action_constraint = None                               # (step Where, k) of action_constrain(), or None
+        self._action_constraint_deep = False                         # action_constrain(.., deep=True): the gate reaches the levels beyond the record buffers
         self.stopped = None                                          # the reason advance() gave for ("stopped", ..)
         self._pruned_checked = 0                                     # the newest filtered level run(never=..) has looked at
         o = capi.Options()
@@ -527,6 +528,8 @@ class ModelChecker:
         self._after_init_filter()
 
     def _after_init_filter(self):
+        if self._action_constraint is not None and self._action_constraint_deep:   # (a search that starts over keeps the attachment and the opt-in; asked for again: harmless)
+            check(capi.load().vsrmc_checker_action_constrain_deep(self._h, 1))
         if self._constraint is not None:
             if self._constraint_deep:                                # (a search that starts over keeps the attachment; the opt-in is asked for again at level 1)
                 check(capi.load().vsrmc_checker_constrain_deep(self._h, 1))
@@ -571,17 +574,23 @@ class ModelChecker:
         self._fresh()
         self._after_init_filter()
 
-    def action_constrain(self, step_where, name=None):
+    def action_constrain(self, step_where, name=None, deep=False):
         """Attach an action constraint (TLC's ACTION_CONSTRAINT; vsrmc_checker_action_constrain_attach): the exported predicate `name` (a name or a number;
         None: the program's only one) of the STEP program `step_where` (Model.compile_step_predicates).  A transition that fails it is generated and
         counted but not taken: its successor is neither put into the seen-set nor stored, and may still be reached by a permitted transition.  Init is
         not subject to it.  At level 1 only (a fresh checker, or after reset()); step_where=None detaches, at any level, and starts over.  A state constraint
         (constrain) may be attached beside it.  While attached, levels are stored only (run(): "constraint-out-of-room" when the next one does not fit);
         deepen / probe / deep_attach / save are refused; every trace takes permitted steps only, and step_scan / step_never / step_reach judge the
-        permitted transitions only (a blocked one is neither counted nor listed, and is never a witness)."""
+        permitted transitions only (a blocked one is neither counted nor listed, and is never a witness).
+        deep=True (vsrmc_checker_action_constrain_deep): the gate reaches the levels beyond the record buffers — the record-less first pass, the level a
+        descent inserts and the probed level take permitted transitions only (k_step_expand's insert, stored and probe modes) — so advance() / run() /
+        check() / deepen() / probe() go on as on an unconstrained checker and run() no longer ends "constraint-out-of-room".
+        action_constraint_deep_results() has the figures of those levels.  Not beside a state constraint, and not with exact_ties, deep_attach /
+        deep_terminal_attach, probe2 / probe3, save."""
         if step_where is None:
             check(capi.load().vsrmc_checker_action_constrain_attach(self._h, None, 0))
             self._action_constraint = None
+            self._action_constraint_deep = False
             self._fresh()
             self._after_init_filter()
             return
@@ -592,6 +601,17 @@ class ModelChecker:
         k = name if isinstance(name, int) else step_where.names.index(name)
         check(capi.load().vsrmc_checker_action_constrain_attach(self._h, step_where._h, k))
         self._action_constraint = (step_where, k)
+        self._action_constraint_deep = False
+        if deep:
+            try:
+                check(capi.load().vsrmc_checker_action_constrain_deep(self._h, 1))
+            except VsrmcError:
+                self._action_constraint = None
+                check(capi.load().vsrmc_checker_action_constrain_attach(self._h, None, 0))   # nothing stays attached by a refused call; the detaching call
+                self._fresh()                                                                # starts the search over, and this object follows it
+                self._after_init_filter()
+                raise
+            self._action_constraint_deep = True
         self._fresh()
         self._after_init_filter()
 
@@ -619,8 +639,40 @@ class ModelChecker:
             try:
                 out.append(one(lv))
             except VsrmcError:
-                return out
+                # (with deep=True the levels beyond the buffers lie between stored ones — action_constraint_deep_results has those — up to the deepest level reached)
+                if not self._action_constraint_deep or lv > max(self.level, self.depth) + 1:
+                    return out
             lv += 1
+
+    def action_constraint_deep_results(self, level=None):
+        """The figures of the gated passes beyond the record buffers (vsrmc_checker_action_constraint_deep_info; action_constrain(.., deep=True)) ->
+        [dict(level, kind in ("inserted-recordless", "inserted", "probed"), parents, pairs, permitted, blocked, blocked_act={action name: n},
+        blocked_violating, blocked_viol_mask, blocked_min_fp, blocked_viol_min_fp, slices, relisted, launches, list_ms, verdict_ms, expand_ms)], ascending;
+        level=L: the passes that led INTO level L.  A probed level is filed anew (kind "inserted") by the pass that inserts it, and its row goes when a stored
+        step after a re-basing files the level in action_constraint_results() instead: the two lists never hold the same level."""
+        if self._action_constraint is None:
+            raise ValueError("no action constraint attached (action_constrain)")
+        none = (1 << 64) - 1
+
+        def one(lv):
+            ai = capi.ActionConstraintDeepInfo()
+            check(capi.load().vsrmc_checker_action_constraint_deep_info(self._h, lv, C.byref(ai)))
+            d = {n: getattr(ai, n) for n, _ in ai._fields_ if n != "blocked_act"}
+            d["kind"] = {1: "inserted-recordless", 2: "inserted", 3: "probed"}[d["kind"]]
+            d["blocked_act"] = {ACTION_NAMES[a]: int(ai.blocked_act[a]) for a in range(16) if ai.blocked_act[a]}
+            for f in ("blocked_min_fp", "blocked_viol_min_fp"):
+                d[f] = None if d[f] == none else int(d[f])
+            return d
+        if level is not None:
+            return one(level)
+        out = []
+        for lv in range(2, max(self.level, self.depth) + 3):
+            try:
+                out.append(one(lv))
+            except VsrmcError as e:
+                if e.code != -1:
+                    raise
+        return out
 
     def seen_set_load(self):
         """(occupied slots, slots) of the seen-set, counted from a copy of the table (vsrmc_checker_seen_set_load)."""

@@ -178,6 +178,14 @@ void action_constraint_restart(vsrmc_checker* c);
 void action_constraint_free(vsrmc_checker* c);
 int action_constraint_trace(vsrmc_checker* c, const std::vector<u64>& fps, u64* words, u64 cap_words, u64* off, int32_t* actions, u64 cap_states, u64* n_states);
 const vsrmc_where* action_constraint_program(const vsrmc_checker* c, int* k);   // the attached step program and its exported predicate; NULL without an attachment
+// ... beyond the record buffers (vsrmc_checker_action_constrain_deep): is the opt-in on?  Then a deep pass in MODE_INSERT, MODE_NORMAL or
+// MODE_PROBE runs through expand_pass_gated in the place of expand_pass (it leaves c->h as expand_pass does), and its caller files the pass's figures under
+// the level it led into (kind: 1 inserted record-less, 2 inserted by a descent, 3 probed); epoch: a new unit of progress starts, figures filed from here on
+// replace what an earlier one left for the same level
+bool action_deep_on(const vsrmc_checker* c);
+int expand_pass_gated(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 n, u64 p_off, int level, int mode, u64 bag, const PassDst* dst);
+void action_deep_file(vsrmc_checker* c, int level, int kind);
+void action_deep_epoch(vsrmc_checker* c);
 typedef void (*ExpandKernel)(Model, const u64*, const u64*, u64, int, int, Slot*, u64, u64*, u64, LevelCtl*, int, int, u64*, u64, u32, u64*,
                              u64, u64*, u64, u64*, u32, u32, int, u32, u64*, u64, u64*, u32, int, u64, const WSet*, u32);
 typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64, Slot*, u64*, u64, u64*, u64, u64*, LevelCtl*,

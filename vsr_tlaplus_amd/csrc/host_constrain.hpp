@@ -195,6 +195,8 @@ int32_t vsrmc_checker_constrain_attach(vsrmc_checker* c, const vsrmc_where* w, i
     constraint_free(c);
     return checker_seed(c);
   }
+  if (action_deep_on(c)) return fail(VSRMC_E_STATE, "constraint: the action constraint is applied beyond the record buffers (vsrmc_checker_action_constrain_deep): the record-less pass there cannot judge states, "
+                                                    "so a state constraint is not taken beside it");
   if (w->prog.step) return fail(VSRMC_E_ARG, "constraint: a step program (vsrmc_step_compile) runs over pairs; a constraint is a state predicate");
   if (!where_fits(w, c->model.M, c->model.symmetry)) return fail(VSRMC_E_ARG, "constraint: compiled for another model");
   if (name_index < 0 || (size_t)name_index >= w->prog.names.size()) return fail(VSRMC_E_ARG, "constraint: the program exports no predicate of that index");

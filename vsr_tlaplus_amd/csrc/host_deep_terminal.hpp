@@ -298,6 +298,7 @@ int32_t vsrmc_checker_deep_terminal_attach(vsrmc_checker* c) {
   if (!c) return fail(VSRMC_E_ARG, "NULL argument");
   if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "deep terminal scan: the constraint is applied beyond the record buffers (vsrmc_checker_constrain_deep): the probed level's successors are judged on arrival, which the terminal attachment does not know about");
   if (c->constraint) return fail(VSRMC_E_STATE, "deep terminal scan: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (action_deep_on(c)) return fail(VSRMC_E_STATE, "deep terminal scan: the action constraint is applied beyond the record buffers (vsrmc_checker_action_constrain_deep): the attached scans read transitions the gate does not take");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "deep terminal scan: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "deep terminal scan: sharded checkers are not scanned (their terminal states stay counted: vsrmc_level_info.deadlocks)");
   if (c->opt.exact_ties) return fail(VSRMC_E_STATE, "deep terminal scan: levels beyond the record buffers need a single-pass checker");

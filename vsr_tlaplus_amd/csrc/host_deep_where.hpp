@@ -296,6 +296,7 @@ int32_t vsrmc_checker_deep_attach(vsrmc_checker* c, const vsrmc_where* state_pro
   }
   if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "deep predicates: the constraint is applied beyond the record buffers (vsrmc_checker_constrain_deep): the probed level's successors are judged on arrival, which the attached scans do not know about");
   if (c->constraint) return fail(VSRMC_E_STATE, "deep predicates: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (action_deep_on(c)) return fail(VSRMC_E_STATE, "deep predicates: the action constraint is applied beyond the record buffers (vsrmc_checker_action_constrain_deep): the attached scans read transitions the gate does not take");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "deep predicates: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (state_prog && state_prog->prog.step) return fail(VSRMC_E_ARG, "deep predicates: a step program in the state position");
   if (step_prog && !step_prog->prog.step) return fail(VSRMC_E_ARG, "deep predicates: a state program in the step position");

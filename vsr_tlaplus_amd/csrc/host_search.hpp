@@ -13,7 +13,8 @@ int32_t vsrmc_checker_probe(vsrmc_checker* c, vsrmc_level_info* info) {
   // not find there (vsrmc_checker_probe_candidates) still have to be shown to their owners (sharded.py: ShardedChecker.probe)
   if (c->opt.exact_ties) return fail(VSRMC_E_STATE, "probe levels need a single-pass checker");
   if (c->constraint && !deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
-  if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint && !action_deep_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint && c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe: a state constraint beside an action constraint that is applied beyond the record buffers: the two together are not taken there");
   if (c->failed && c->failed_code != ERR_FRONTIER_FULL) return fail(VSRMC_E_STATE, "the checker stopped on an error");
   c->failed = 0;
   c->probe_fp = 0;
@@ -22,7 +23,19 @@ int32_t vsrmc_checker_probe(vsrmc_checker* c, vsrmc_level_info* info) {
   c->probe_viol.clear();
   c->probe_viol_key.clear();
   c->probe_viol_level = 0;
-  int rc = phase_expand(c, nullptr, MODE_PROBE);
+  const bool gated = action_deep_on(c);                         // the probed level's candidates are the successors of PERMITTED transitions
+  int rc = 0;
+  if (gated) {
+    HIPCHK(hipSetDevice(c->opt.device));
+    c->t_level0 = now_s();
+    c->expand_ms = 0;
+    action_deep_epoch(c);
+    rc = expand_pass_gated(c, c->words[c->cur], c->off[c->cur], c->n_frontier, 0, c->level + 1, MODE_PROBE, c->bag_known ? c->cur_max_bag : (u64)c->model.M.max_bag, nullptr);
+    if (!rc) action_deep_file(c, c->level + 1, 3);
+    if (!rc && c->h.n_pending > c->opt.pending_entries) rc = fail(VSRMC_E_REP, "more violating successors in the probed level than the pending list holds (pending_entries)");
+  } else {
+    rc = phase_expand(c, nullptr, MODE_PROBE);
+  }
   u64 rechecked = 0;
   if (!rc && c->h.limit_unchecked) {                            // (see LevelCtl::limit_unchecked: the pass once more with every action applied)
     rechecked = c->h.limit_unchecked;
@@ -130,6 +143,7 @@ int32_t vsrmc_checker_probe_trace(vsrmc_checker* c, uint64_t* words, uint64_t ca
   int rc = walk_trace(c, c->probe_fp, c->probe_level, &fps);    // Init .. the deepest state of the path that is in the seen-set
   if (rc) return rc;
   if (c->probe_extra_fp) fps.push_back(c->probe_extra_fp);      // ... and the probed state beyond it
+  if (c->action_constraint) return action_constraint_trace(c, fps, words, cap_words, off, actions, cap_states, n_states);   // (permitted steps only, the last one included)
   return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
 }
 
@@ -150,6 +164,7 @@ int trace_by_parent_key(vsrmc_checker* c, u64 fp, u64 key, int plevel, uint64_t*
   rc = walk_trace(c, pfp, plevel - 1, &fps);
   if (rc) return rc;
   fps.push_back(fp);
+  if (c->action_constraint) return action_constraint_trace(c, fps, words, cap_words, off, actions, cap_states, n_states);
   return vsrmc_model_replay_fps(&c->model, c->opt.device, fps.data(), (int32_t)fps.size(), words, cap_words, off, actions, cap_states, n_states);
 }
 }  // namespace
@@ -246,9 +261,13 @@ static int adopt_overflowed_level(vsrmc_checker* c, vsrmc_level_info* ins) {
        hipMemcpy(sums, d, 24, hipMemcpyDeviceToHost) == hipSuccess;
   (void)hipFree(d);
   if (!ok) return fail(VSRMC_E_HIP, "k_table_level_checksum failed");
-  if (sums[2] != h.n_written)                                   // every claim wrote (or tried to write) one record: the two counts are one number
+  // every claim wrote (or tried to write) one record: the two counts are one number.  (Through the gate, k_step_expand: a wave that finds no room writes
+  // nothing and counts nothing in n_written, but every claim was counted in n_new before the room was looked at — that is the level's size.)
+  const u64 claimed = c->action_constraint ? h.n_new : h.n_written;
+  if (sums[2] != claimed)
     return fail(VSRMC_E_STATE, "adopting an overflowed level: the seen-set holds " + std::to_string((unsigned long long)sums[2]) +
-                               " states of the level, the kernel claimed " + std::to_string((unsigned long long)h.n_written));
+                               " states of the level, the kernel claimed " + std::to_string((unsigned long long)claimed));
+  if (action_deep_on(c)) { action_deep_epoch(c); action_deep_file(c, c->level + 1, 1); }   // the overflowed gated step's figures (phase_expand_gated left them)
   c->failed = 0;
   c->failed_code = 0;
   c->full_recoverable = false;
@@ -371,7 +390,7 @@ int32_t vsrmc_checker_advance(vsrmc_checker* c, vsrmc_level_info* a, vsrmc_level
   std::memset(b, 0, sizeof(*b));
   b->viol_fp = b->viol_index = ~(u64)0;
   if (c->opt.world > 1) return fail(VSRMC_E_STATE, "sharded checker: vsrmc_shard_loop_advance");
-  if ((c->constraint && !deep_constrain_on(c)) || c->action_constraint) {   // levels are stored, or the run ends (vsrmc_checker_constrain_deep lifts that for a state constraint): no deep pass runs over a half-filtered search
+  if ((c->constraint && !deep_constrain_on(c)) || (c->action_constraint && !action_deep_on(c))) {   // levels are stored, or the run ends (vsrmc_checker_constrain_deep / _action_constrain_deep lift that): no deep pass runs over a half-filtered search
     auto no_room = [&](const char* why) {
       *what = 4;
       std::memset(a, 0, sizeof(*a));

@@ -20,6 +20,17 @@
 //   wave's leader lanes add to, and reaches the control blocks once per wave resp. block at the end of the launch.
 //   `live` (one u32 per parent of the slice, zeroed by the host): the first listed instance of a parent flips it, so that the host has the level's
 //   deadlocks as parents scanned minus parents with an instance — the figure k_expand's enumeration leaves in LevelCtl::deadlocks.
+//
+// Beyond the record buffers (expand_pass_gated, host_action_constrain.hpp) the same kernel runs in one of three compile-time modes:
+//   GATE_STORED  the code above, unchanged: a stored level, and the level a descent inserts into a scratch buffer (the destination and its caps are the buffer's)
+//   GATE_INSERT  the record-less first pass: the permitted successors are claimed exactly as above and NOTHING is written — no room is reserved, so the two
+//                atomics per wave and trip are gone.  The claiming lane evaluates the invariants; n_new, fp_xor, fp_sum and max_bag live in registers over the
+//                grid-stride loop and reach LevelCtl with one atomic per counter and wave at the end of the launch.  A violator is appended to `pending` as
+//                (fingerprint, key) through wave_alloc — only a trip in which a lane has one issues that atomic.
+//   GATE_PROBE   no claim: a permitted successor is looked up and dropped if it is a state of an earlier level; otherwise the invariants are evaluated and a
+//                violator goes to `pending` and viol_fp / viol_mask, for deep_resolve (vsr_deep.hpp) as k_expand's MODE_PROBE leaves them.
+//   In the last two modes nx_words / nx_words_cap carry the pending list and its capacity in ENTRIES (the kernel writes no record), nx_off, nx_cap and lvl_fp
+//   are unused, and under VSRMC_TEST_HOOKS the state Model::test_bad_fp names fails Model::test_bad_mask, as in the general k_expand.
 #pragma once
 #include "vsr_kernels.hpp"
 #include "vsr_step.hpp"
@@ -74,7 +85,9 @@ __device__ __forceinline__ void actc_write_child(const Model& M, const u64* rec,
     }
 }
 
-template <int MODEL>
+enum { GATE_STORED = 0, GATE_INSERT = 1, GATE_PROBE = 2 };
+
+template <int MODEL, int GATE = GATE_STORED>
 __global__ void __launch_bounds__(256)
 k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ refs, const u64* __restrict__ list, const u32* __restrict__ rows, u64 n_entries,
               int k_bit, int level, u64 lo, Slot* table, u64 tmask, u64* nx_words, u64 nx_words_cap, u64* nx_off, u64 nx_cap, u64* lvl_fp, LevelCtl* ctl,
@@ -88,6 +101,8 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
   u64 rec_words = 0;                                                                 // wave-uniform
   u32 probes = 0, n_ties = 0, bag = 0, bmask = 0, vmask = 0;                         // per lane, reduced at the end
   u64 vmin = ~(u64)0, bmin = ~(u64)0, bvmin = ~(u64)0;
+  u32 n_claimed = 0;                                                                 // GATE_INSERT, per lane: the level's states, their xor and sum
+  u64 fxor = 0, fsum = 0;
   const u64 step = (u64)gridDim.x * blockDim.x;
   const u64 n_round = (n_entries + 63) & ~(u64)63;                 // whole waves stay together
   for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < n_round; e += step) {
@@ -121,31 +136,70 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
     if (bb) {                                                      // (wave-uniform)
       n_blocked += (u32)__popcll(bb);
       actc_count_actions(s_blk, blocked, action, lane);
-      const int bad = blocked ? Ops::invariants(M, rec, D) : 0;
+      int bad = blocked ? Ops::invariants(M, rec, D) : 0;
+#ifdef VSRMC_TEST_HOOKS
+      if (blocked && M.test_bad_mask) {                            // test hook (Model::test_bad_fp): a blocked successor is not fingerprinted — except here, to count it
+        u64 Hb[6], bfp;
+        u32 bak;
+        Ops::hash_child_(M, rec, D, Hb);
+        canonical_fp(M, D.hdr, Hb, &bfp, &bak);
+        if (bfp == M.test_bad_fp) bad |= (int)M.test_bad_mask;
+      }
+#endif
       n_bviol += (u32)__popcll(__ballot(bad != 0));
       if (blocked) {
         bmin = pfp < bmin ? pfp : bmin;
         if (bad) { bmask |= (u32)bad; bvmin = pfp < bvmin ? pfp : bvmin; }
       }
     }
-    // the transitions taken: fingerprint, claim, and the claiming lane's reservation
+    // the transitions taken: fingerprint, claim (GATE_PROBE: lookup), and the claiming lane's reservation
     bool claimed = false;
     u64 fp = 0, Hc[6];
     int clen = 0;
+    [[maybe_unused]] u64 key = 0;
     if (permitted) {
       Ops::hash_child_(M, rec, D, Hc);
       u32 ak;
       canonical_fp(M, D.hdr, Hc, &fp, &ak);
-      const u64 key = meta_make(level, ak, pfp);
-      bool full = false;
-      u64 prev_meta = META_EMPTY;
-      table_claim_fused(table, tmask, fp, key, level, &claimed, &prev_meta, CntReg{&probes}, &full);
-      if (full) {
-        raise_error(ctl, ERR_TABLE_FULL, fp);
-        claimed = false;
+      key = meta_make(level, ak, pfp);
+      if constexpr (GATE == GATE_PROBE) {
+        u64 m = META_EMPTY;
+        claimed = !(probe_lookup(table, tmask, fp, &m, CntReg{&probes}) && meta_level(m) < level);   // (here: not a state of an earlier level — a candidate)
+      } else {
+        bool full = false;
+        u64 prev_meta = META_EMPTY;
+        table_claim_fused(table, tmask, fp, key, level, &claimed, &prev_meta, CntReg{&probes}, &full);
+        if (full) {
+          raise_error(ctl, ERR_TABLE_FULL, fp);
+          claimed = false;
+        }
+        if (!full && prev_meta != META_EMPTY && meta_level(prev_meta) == level && meta_auxkey(prev_meta) != meta_auxkey(key)) n_ties++;
+        if (claimed) clen = M.fixed + hdr_nmsg(D.hdr);
       }
-      if (!full && prev_meta != META_EMPTY && meta_level(prev_meta) == level && meta_auxkey(prev_meta) != meta_auxkey(key)) n_ties++;
-      if (claimed) clen = M.fixed + hdr_nmsg(D.hdr);
+    }
+    if constexpr (GATE != GATE_STORED) {                           // nothing is written: counted and checked in registers, a violator listed
+      int bad = 0;
+      if (claimed) {
+        bad = Ops::invariants(M, rec, D);
+#ifdef VSRMC_TEST_HOOKS
+        if (M.test_bad_mask && fp == M.test_bad_fp) bad |= (int)M.test_bad_mask;   // test hook (Model::test_bad_fp)
+#endif
+        if constexpr (GATE == GATE_INSERT) {
+          n_claimed++;
+          fxor ^= fp;
+          fsum += fp;
+          bag = max(bag, (u32)hdr_nmsg(D.hdr));
+        }
+        if (bad) { vmask |= (u32)bad; vmin = fp < vmin ? fp : vmin; }
+      }
+      if (bad) {                                                   // (divergent: wave_alloc counts the lanes that are here; no lane, no atomic)
+        const u64 i = wave_alloc(&ctl->n_pending);
+        if (i < nx_words_cap) {
+          nx_words[2 * i] = fp;
+          nx_words[2 * i + 1] = key;
+        }
+      }
+      continue;                                                    // (every lane of the wave: nothing above leaves the loop)
     }
     const u64 cb = __ballot(claimed);
     if (cb == 0) continue;                                         // (wave-uniform)
@@ -165,6 +219,16 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
     }
     ibase = readlane64(ibase, 0);
     wbase = readlane64(wbase, 0);
+    // the claiming lane checks its state BEFORE the room is looked at: a level that overflows the buffers is complete in the seen-set, counted in n_new and
+    // checked all the same, so that the host can keep it as a seen-set-only level (adopt_overflowed_level)
+    if (claimed) {
+      bag = max(bag, (u32)hdr_nmsg(D.hdr));
+      int bad = Ops::invariants(M, rec, D);
+#ifdef VSRMC_TEST_HOOKS
+      if (M.test_bad_mask && fp == M.test_bad_fp) bad |= (int)M.test_bad_mask;   // test hook (Model::test_bad_fp): a violator on a level that overflows
+#endif
+      if (bad) { vmask |= (u32)bad; vmin = fp < vmin ? fp : vmin; }
+    }
     if (ibase + cnt > nx_cap || wbase + total > nx_words_cap) {    // (wave-uniform) out of index or word room: nothing of this wave is written
       if (lane == 0) raise_full(ctl, pidx);
       continue;
@@ -177,14 +241,14 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
       actc_write_child(M, rec, D, Hc, nx_words + dst);
       nx_off[idx] = (dst << 8) | (u64)clen;
       lvl_fp[idx] = fp;
-      bag = max(bag, (u32)hdr_nmsg(D.hdr));
-      const int bad = Ops::invariants(M, rec, D);
-      if (bad) { vmask |= (u32)bad; vmin = fp < vmin ? fp : vmin; }
     }
   }
   // the end of the launch: every lane of the wave is here (the loop above only `continue`s at wave-uniform points); one reduction and one atomic per counter and wave
   const u32 w_probes = wave_sum32(probes), w_ties = wave_sum32(n_ties), w_bag = wave_max32(bag), w_vmask = wave_or32(vmask), w_bmask = wave_or32(bmask);
   const u64 w_vmin = wave_min64(vmin), w_bmin = wave_min64(bmin), w_bvmin = wave_min64(bvmin);
+  [[maybe_unused]] u32 w_claimed = 0;
+  [[maybe_unused]] u64 w_fxor = 0, w_fsum = 0;
+  if constexpr (GATE == GATE_INSERT) { w_claimed = wave_sum32(n_claimed); w_fxor = wave_xor64(fxor); w_fsum = wave_sum64(fsum); }
   if (lane == 0) {
     if (n_gen) atomicAdd((unsigned long long*)&ctl->generated, (unsigned long long)n_gen);
     if (n_written) atomicAdd((unsigned long long*)&ctl->n_written, (unsigned long long)n_written);
@@ -195,6 +259,13 @@ k_step_expand(Model M, const u64* __restrict__ words, const u64* __restrict__ re
     if (w_vmask) {
       atomicMin((unsigned long long*)&ctl->viol_fp, (unsigned long long)w_vmin);
       atomicOr(&ctl->viol_mask, w_vmask);
+    }
+    if constexpr (GATE == GATE_INSERT) {                           // the level's size and checksums: what k_expand's MODE_INSERT leaves (no lvl_fp array exists)
+      if (w_claimed) {
+        atomicAdd((unsigned long long*)&ctl->n_new, (unsigned long long)w_claimed);
+        atomicXor((unsigned long long*)&ctl->fp_xor, (unsigned long long)w_fxor);
+        atomicAdd((unsigned long long*)&ctl->fp_sum, (unsigned long long)w_fsum);
+      }
     }
     if (n_live) atomicAdd((unsigned long long*)&actl->live_parents, (unsigned long long)n_live);
     if (n_blocked) {

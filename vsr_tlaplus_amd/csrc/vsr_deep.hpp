@@ -199,6 +199,11 @@ void deep_acc(vsrmc_level_info* t, const LevelCtl& h, double ms) {
 int deep_run_pass(DeepRun& R, const u64* sw, const u64* so, u64 n, u64 p_off, int level, int mode, u64 bag, const PassDst* dst) {
   R.c->extra_launches = 0;
   if (R.io) return R.io->pass(R.io->ctx, sw, so, n, p_off, level, mode, bag, dst);
+  if (mode != MODE_REGEN && action_deep_on(R.c)) {               // the action constraint reaches these levels (host_action_constrain.hpp): permitted transitions only.  A
+    const int rc = expand_pass_gated(R.c, sw, so, n, p_off, level, mode, bag, dst);   // regenerating pass needs no gate: it takes a state only under the key a permitted transition wrote
+    if (!rc) action_deep_file(R.c, level, mode == MODE_INSERT ? 1 : 2);
+    return rc;
+  }
   return expand_pass(R.c, sw, so, n, p_off, level, mode, bag, dst);   // (expand_pass finds the claim bitmap of the first seen-set-only level by itself)
 }
 
@@ -207,6 +212,7 @@ int deep_run_pass(DeepRun& R, const u64* sw, const u64* so, u64 n, u64 p_off, in
 void deep_claim_bits_alloc(vsrmc_checker* c, u64 src_max_bag) {
   if (c->claim_bits) { (void)hipFree(c->claim_bits); c->claim_bits = nullptr; }
   c->claim_w = c->claim_parents = 0;
+  if (c->action_constraint) return;                              // (the gated insert, k_step_expand, leaves no bitmap: regeneration asks the seen-set)
   if (c->opt.world > 1 || !c->regen_bits_kernel || !c->insert_kernel) return;   // (two instantiations of k_expand know the bitmap)
   const Model& M = c->model.M;
   const u64 ords = (u64)M.m0 + std::min<u64>(src_max_bag, (u64)M.max_bag) * (u64)(M.R + 1) + 1;
@@ -241,7 +247,10 @@ int deep_probe(DeepRun& R, const PassDst& B, u64 n, int lv, u64 bag) {
   if (!n) return 0;
   c->expand_ms = 0;
   if (R.err) return 0;
-  int rc = expand_pass(c, B.words, B.off, n, 0, lv + 1, MODE_PROBE, bag);
+  const bool gated = action_deep_on(c);                         // only successors of permitted transitions are candidates (a listed instance's error arrives in its
+  int rc = gated ? expand_pass_gated(c, B.words, B.off, n, 0, lv + 1, MODE_PROBE, bag, nullptr)   // `rows` word: no footprint filter, so no second run — limit_unchecked stays 0)
+                 : expand_pass(c, B.words, B.off, n, 0, lv + 1, MODE_PROBE, bag);
+  if (gated && !rc) action_deep_file(c, lv + 1, 3);
   R.launches += c->extra_launches;
   if (!rc && c->h.limit_unchecked) {                            // a record at a representation limit beside instances the footprint filter skipped: once more, every action applied
     R.prb.limit_rechecked += c->h.limit_unchecked;
@@ -679,7 +688,9 @@ extern "C" {
 int32_t vsrmc_checker_deepen(vsrmc_checker* c, vsrmc_level_info* inserted, vsrmc_level_info* probed) {
   if (!c || !inserted || !probed) return fail(VSRMC_E_ARG, "NULL argument");
   if (c->constraint && !deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
-  if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint && !action_deep_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (c->action_constraint && c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_deepen: a state constraint beside an action constraint that is applied beyond the record buffers: the two together are not taken there");
+  action_deep_epoch(c);
   int rc = deep_check_ready(c, 2, false);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->opt.device));
@@ -703,6 +714,7 @@ int32_t vsrmc_checker_probe2(vsrmc_checker* c, vsrmc_level_info* virt, vsrmc_lev
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2 starts from a materialised level");
   if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: the constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance only (vsrmc_checker_constrain_deep): this path does not filter");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (action_deep_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: the action constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance / _probe only (vsrmc_checker_action_constrain_deep): this path does not gate");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   if (c->deep_term) return fail(VSRMC_E_STATE, "vsrmc_checker_probe2: the terminal attachment (vsrmc_checker_deep_terminal_attach) scans the passes of vsrmc_checker_deepen / _advance");
@@ -719,6 +731,7 @@ int32_t vsrmc_checker_probe3(vsrmc_checker* c, vsrmc_level_info* virt1, vsrmc_le
   if (c->deep) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3 starts from a materialised level");
   if (deep_constrain_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: the constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance only (vsrmc_checker_constrain_deep): this path does not filter");
   if (c->constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: a constraint is attached (vsrmc_checker_constrain_attach): the levels beyond the record buffers are not constrained");
+  if (action_deep_on(c)) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: the action constraint is applied beyond the record buffers by vsrmc_checker_deepen / _advance / _probe only (vsrmc_checker_action_constrain_deep): this path does not gate");
   if (c->action_constraint) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: an action constraint is attached (vsrmc_checker_action_constrain_attach): the levels beyond the record buffers are not constrained");
   if (c->deep_attach) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: predicates are attached (vsrmc_checker_deep_attach): they are evaluated by vsrmc_checker_deepen / _advance");
   if (c->deep_term) return fail(VSRMC_E_STATE, "vsrmc_checker_probe3: the terminal attachment (vsrmc_checker_deep_terminal_attach) scans the passes of vsrmc_checker_deepen / _advance");

@@ -126,6 +126,11 @@ static void usage() {
       "                    -stepReach, -checkDeadlock and -dumpTrace.  Levels are stored only, as with -constraint (exit 4 when the next one does not fit).\n"
       "                    Not with -gpus N > 1, -simulate, -deepPredicates, -probeLast, -probe2At, -probe3At, -checkpoint, -recover, -audit.  With -json the\n"
       "                    level lines carry \"permitted\" and \"blocked\"\n"
+      "  -deepActionConstraint  with -actionConstraint NAME: the action constraint is applied on the levels beyond the record buffers as well (the record-less\n"
+      "                    first pass, the level a descent inserts and the probed level take permitted transitions only), so the run goes on past them instead of\n"
+      "                    ending with exit 4.  The Virtual and Probe lines then carry the transitions not taken, and the closing line's totals include those\n"
+      "                    levels.  Not with -constraint, -deepPredicates, -deepTerminal, -probeLast, -probe2At, -probe3At, -checkpoint, -recover,\n"
+      "                    -audit, -gpus N > 1\n"
       "  -json             one JSON object per level on stdout instead of TLC-style progress lines\n");
 }
 
@@ -176,7 +181,7 @@ static bool write_trace_expression(const std::string& path, const vsrmc_model* m
 }
 
 int main(int argc, char** argv) {
-  bool deep_terminal = false, deep_constraint = false;
+  bool deep_terminal = false, deep_constraint = false, deep_action = false;
   bool deep_predicates = false, constrained = false, action_constrained = false, walk_constrained = false, walk_action_constrained = false;
   for (int i = 1; i < argc; i++) {
     if (std::string(argv[i]) == "-walkConstraint") walk_constrained = true;
@@ -186,6 +191,7 @@ int main(int argc, char** argv) {
     if (std::string(argv[i]) == "-constraint") constrained = true;
     if (std::string(argv[i]) == "-deepConstraint") deep_constraint = true;
     if (std::string(argv[i]) == "-actionConstraint") action_constrained = true;
+    if (std::string(argv[i]) == "-deepActionConstraint") deep_action = true;
   }
   for (int i = 1; i + 1 < argc; i++)
     if (std::string(argv[i]) == "-gpus" && std::atoi(argv[i + 1]) > 1) {
@@ -257,6 +263,7 @@ int main(int argc, char** argv) {
     else if (a == "-deepPredicates") deep_predicates = true;
     else if (a == "-deepTerminal") deep_terminal = true;
     else if (a == "-deepConstraint") deep_constraint = true;
+    else if (a == "-deepActionConstraint") deep_action = true;
     else if (a == "-workers" && i + 1 < argc) ++i;   // accepted for command-line compatibility; the GPU is the worker pool
     else if (!a.empty() && a[0] != '-') tla = a;
     else { std::fprintf(stderr, "vsrmc: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -268,6 +275,14 @@ int main(int argc, char** argv) {
                       : deep_predicates ? "-deepConstraint cannot be combined with -deepPredicates: the probed level's successors are judged on arrival, which the attached scans do not know about"
                       : deep_terminal ? "-deepConstraint cannot be combined with -deepTerminal: the probed level's successors are judged on arrival, which the terminal attachment does not know about"
                       : (probe2_at > 0 || probe3_at > 0) ? "-deepConstraint cannot be combined with -probe2At / -probe3At: those passes do not filter" : nullptr;
+    if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
+  }
+  if (deep_action) {                                              // refused before any device call
+    const char* why = !action_constrained ? "-deepActionConstraint needs -actionConstraint NAME: it is that constraint which is applied beyond the record buffers"
+                      : constrained ? "-deepActionConstraint cannot be combined with -constraint: the record-less pass beyond the record buffers cannot judge states"
+                      : deep_predicates ? "-deepActionConstraint cannot be combined with -deepPredicates: the attached scans read transitions the gate does not take"
+                      : deep_terminal ? "-deepActionConstraint cannot be combined with -deepTerminal: the terminal attachment scans passes that do not know the gate"
+                      : (probe_last || probe2_at > 0 || probe3_at > 0) ? "-deepActionConstraint cannot be combined with -probeLast / -probe2At / -probe3At: those passes do not gate" : nullptr;
     if (why) { std::fprintf(stderr, "Error: %s\n", why); return 2; }
   }
   if (constrained) {                                              // refused before any device call
@@ -722,6 +737,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
     return 1;
   }
+  if (s_act && deep_action && vsrmc_checker_action_constrain_deep(c, 1) != 0) {
+    std::fprintf(stderr, "Error: %s\n", vsrmc_last_error());
+    return 1;
+  }
   static const char* const MODULES[3] = {"VSR.tla", "VR_STATE_TRANSFER.tla", "VR_APP_STATE.tla"};
   std::printf("vsrmc: %s lowered: ReplicaCount=%d ClientCount=%d |Values|=%d StartViewOnTimerLimit=%d, %d permutation(s), "
               "invariant mask %d\n", MODULES[lay.module >= 0 && lay.module < 3 ? lay.module : 0], lay.replica_count, lay.client_count, lay.value_count, lay.start_view_on_timer_limit,
@@ -822,6 +841,19 @@ int main(int argc, char** argv) {
     act_blocked_total += (unsigned long long)act_info.blocked;
     act_blocked_violating += (unsigned long long)act_info.blocked_violating;
     for (int a2 = 0; a2 < 16; a2++) act_blocked_by[a2] += (unsigned long long)act_info.blocked_act[a2];
+    return true;
+  };
+  // -deepActionConstraint: the gated passes into a level beyond the record buffers (an inserted level joins the totals; a probed one is printed only — the pass
+  // that inserts it counts it)
+  vsrmc_action_constraint_deep_info act_deep;
+  std::memset(&act_deep, 0, sizeof(act_deep));
+  auto act_collect_deep = [&](int level, bool inserted) -> bool {
+    if (!s_act || !deep_action || vsrmc_checker_action_constraint_deep_info(c, level, &act_deep) != 0) return false;
+    if (inserted) {
+      act_blocked_total += (unsigned long long)act_deep.blocked;
+      act_blocked_violating += (unsigned long long)act_deep.blocked_violating;
+      for (int a2 = 0; a2 < 16; a2++) act_blocked_by[a2] += (unsigned long long)act_deep.blocked_act[a2];
+    }
     return true;
   };
   unsigned long long cov[16] = {0};
@@ -1139,6 +1171,7 @@ int main(int argc, char** argv) {
       if (dump) { std::printf("Level %d is not stored (it does not fit the record buffers): -dump ends at level %d.\n", info.level, depth); std::fclose(dump); dump = nullptr; }
       con_info.level = 0;
       if (deep_constraint) con_collect_deep(info.n_new ? info.level : info.level + 1);   // (first: a level that was inserted unfiltered gets its Filtered line before the Virtual line of the level above it)
+      const bool act_deep_new = act_collect_deep(info.n_new ? info.level : info.level + 1, true);   // (an empty level: the pass into it blocked what it blocked)
       if (info.n_new == 0 && !info.viol_mask) break;
       if (info.n_new) depth = info.level;
       if (info.n_new) rows.push_back(Row{info.level, (unsigned long long)info.n_new, (unsigned long long)info.generated, (unsigned long long)info.deadlocks});
@@ -1151,6 +1184,10 @@ int main(int argc, char** argv) {
                     "\"pruned\": %llu, \"seconds\": %.4f}\n", info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
                     (unsigned long long)info.deadlocks, (unsigned long long)info.pending, con_info.level == info.level ? "true" : "false",
                     con_info.level == info.level ? (unsigned long long)con_info.kept : 0ull, con_info.level == info.level ? (unsigned long long)con_info.pruned : 0ull, dtp);
+      else if (json && act_deep_new)
+        std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"permitted\": %llu, "
+                    "\"blocked\": %llu, \"seconds\": %.4f}\n", info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
+                    (unsigned long long)info.deadlocks, (unsigned long long)info.pending, (unsigned long long)act_deep.permitted, (unsigned long long)act_deep.blocked, dtp);
       else if (json)
         std::printf("{\"level\": %d, \"stored\": false, \"generated\": %llu, \"new\": %llu, \"distinct\": %llu, \"deadlocks\": %llu, \"launches\": %llu, \"seconds\": %.4f}\n",
                     info.level, (unsigned long long)info.generated, (unsigned long long)info.n_new, (unsigned long long)info.distinct,
@@ -1162,6 +1199,10 @@ int main(int argc, char** argv) {
       else if (deep_constraint)
       std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches); not judged yet: the next pass filters it. (%.2f s)\n", info.level,
                   (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending, dtp);
+      else if (act_deep_new)
+      std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches); %llu of %llu transitions were not taken. (%.2f s)\n",
+                  info.level, (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending,
+                  (unsigned long long)act_deep.blocked, (unsigned long long)act_deep.pairs, dtp);
       else
       std::printf("Virtual(%d): %llu states generated, %llu distinct states found, %llu states in the level (not stored; %llu launches). (%.2f s)\n", info.level,
                   (unsigned long long)info.total_generated, (unsigned long long)info.distinct, (unsigned long long)info.n_new, (unsigned long long)info.pending, dtp);
@@ -1171,9 +1212,16 @@ int main(int argc, char** argv) {
       if (info.viol_mask && !(dead_here && deep_dead.level < info.level)) { probed_violation = true; viol_level = (uint64_t)info.level; break; }
       if (info.viol_mask) { info.viol_mask = 0; deadlocked = true; break; }
       if (probed.level) {
-        if (json)
+        const bool act_prb = act_collect_deep(probed.level, false);
+        if (json && act_prb)
+          std::printf("{\"probed_level\": %d, \"generated\": %llu, \"from\": %llu, \"violating_successors\": %llu, \"blocked\": %llu, \"seconds\": %.4f}\n", probed.level,
+                      (unsigned long long)probed.generated, (unsigned long long)probed.frontier, (unsigned long long)probed.pending, (unsigned long long)act_deep.blocked, dtp);
+        else if (json)
           std::printf("{\"probed_level\": %d, \"generated\": %llu, \"from\": %llu, \"violating_successors\": %llu, \"seconds\": %.4f}\n", probed.level,
                       (unsigned long long)probed.generated, (unsigned long long)probed.frontier, (unsigned long long)probed.pending, dtp);
+        else if (act_prb)
+        std::printf("Probe(%d): %llu states generated from %llu states, %llu of them by transitions not taken, %llu violating successors seen. (%.2f s)\n", probed.level,
+                    (unsigned long long)probed.generated, (unsigned long long)probed.frontier, (unsigned long long)act_deep.blocked, (unsigned long long)probed.pending, dtp);
         else
         std::printf("Probe(%d): %llu states generated from %llu states, %llu violating successors seen. (%.2f s)\n", probed.level,
                     (unsigned long long)probed.generated, (unsigned long long)probed.frontier, (unsigned long long)probed.pending, dtp);
