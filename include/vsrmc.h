@@ -622,6 +622,11 @@ int32_t vsrmc_checker_probe_candidates(vsrmc_checker* c, uint64_t* pairs, uint64
  * a KNOWN violating state (the last state of the reference's state_transfer_violation_trace.txt:556-577) is among the ones the search met, not
  * only which one it reports.  fps == NULL asks for the number only. */
 int32_t vsrmc_checker_probe_violators(vsrmc_checker* c, uint64_t* fps, uint64_t cap, uint64_t* n);
+/* How many regenerating passes of the deep search this checker has run with the kernel of their own (csrc/vsr_regen_bits.hpp: VSR.tla with R <= 3, one rank,
+ * the claim bitmap of the first seen-set-only level) since it was created; the others ran k_expand's regenerating instantiation.  The environment variable
+ * VSRMC_NO_REGEN_KERNEL, read when the checker is created, keeps it at 0.  (Test knob, read the same way: VSRMC_REGEN_TRIP=N, 1 .. 64, the instances a wave
+ * of that kernel takes per trip.) */
+int32_t vsrmc_checker_regen_launches(const vsrmc_checker* c, uint64_t* n);
 /* seen[i] = 1 if fps[i] is in this checker's seen-set as a state of a level below `level` (host arrays) */
 int32_t vsrmc_checker_seen_batch(vsrmc_checker* c, const uint64_t* fps, uint64_t n, int32_t level, uint8_t* seen);
 int32_t vsrmc_checker_probe_trace(vsrmc_checker* c, uint64_t* words, uint64_t cap_words, uint64_t* off, int32_t* actions,

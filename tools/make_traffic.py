@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def hot(name):   # the kernels of the BFS passes: every k_expand instantiation and the probe pass's own pair (csrc/vsr_probe_scan.hpp)
-    return "k_expand" in name or "k_probe_scan" in name or "k_probe_apply" in name
+def hot(name):   # the kernels of the BFS passes: every k_expand instantiation, the probe pass's own pair (csrc/vsr_probe_scan.hpp) and the regenerating pass's kernel (csrc/vsr_regen_bits.hpp)
+    return "k_expand" in name or "k_probe_scan" in name or "k_probe_apply" in name or "k_regen_bits" in name
 
 
 def sums(path):
@@ -42,7 +42,7 @@ def main():
     wr_bytes = 64 * w64 + 32 * (nwr - w64)
     print(json.dumps(dict(
         source="rocprofv3 --kernel-trace --pmc (two passes: TCC_EA0_RDREQ by size; TCC_EA0_WRREQ, _64B) -- %s (%s)" % (cmd, tag),
-        workload=workload, kernel="k_expand (every instantiation launched by the run) + k_probe_scan / k_probe_apply", launches=int(calls),
+        workload=workload, kernel="k_expand (every instantiation launched by the run) + k_probe_scan / k_probe_apply + k_regen_bits", launches=int(calls),
         rdreq=dict(n32=n32, n64=n64, n128=n128, total=nrd, unsized=other), wrreq=dict(n64=w64, total=nwr),
         atomics_to_fabric=wr.get("TCC_EA0_ATOMIC_sum"), read_bytes=rd_bytes, write_bytes=wr_bytes,
         hbm_bytes_per_launch=round((rd_bytes + wr_bytes) / max(1, calls)), kernel_source_sha256=bench.kernel_source_sha256()), indent=1))

@@ -1422,6 +1422,12 @@ class ModelChecker:
                 self.violation = dict(level=d["level"], index=None, fp=d["viol_fp"], mask=d["viol_mask"], probed=True)
         return tuple(out)
 
+    def regen_launches(self):
+        """Regenerating passes of the deep search this checker has run with the kernel of their own (csrc/vsr_regen_bits.hpp) since it was created."""
+        n = C.c_uint64()
+        check(capi.load().vsrmc_checker_regen_launches(self._h, C.byref(n)))
+        return n.value
+
     def probe_violators(self):
         """fingerprints (ascending) of the distinct violating states of the level the last probe / deepen / advance call probed"""
         n = C.c_uint64()

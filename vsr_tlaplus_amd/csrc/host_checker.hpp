@@ -69,6 +69,12 @@ struct vsrmc_checker {
   u64* probe_list = nullptr;             // PSCAN_LIST_HDR words (word 0: entries appended) + probe_list_cap entries, allocated with the checker
   u64 probe_list_cap = 0;
   bool probe_scan_off = false;           // the pass in flight overflowed the list: it is being run again by the mode-capable k_expand
+  // the regenerating pass over the claim bitmap as a kernel of its own (vsr_regen_bits.hpp; R <= 3).  Null where the configuration has none (or
+  // VSRMC_NO_REGEN_KERNEL is set): k_expand<.., EXPAND_REGEN_BITS> then.  regen_trip: instances a wave takes per trip (VSRMC_REGEN_TRIP, a test knob)
+  void* regen_kernel = nullptr;
+  u32 regen_trip = 64;
+  u64 regen_launches = 0;                // launches of that kernel since the checker was created (vsrmc_checker_regen_launches)
+  u64 regen_dst_states = 0, regen_dst_words = 0;   // test knobs (VSRMC_REGEN_DST_STATES / _WORDS): the most of its destination a regenerating pass is handed, 0 = all of it
   u64 cur_max_bag = 0;                   // largest bag among the records of the newest level (LDS slot size of the next launch)
   bool bag_known = true;                 // false after a checkpoint was loaded or records arrived from other ranks: use the capacity
   // vsrmc_checker_probe / _probe2: where the reported violator's counter-example is walked from — the fingerprint of the deepest
@@ -192,6 +198,7 @@ typedef void (*MaterializeKernel)(Model, const u64*, const u64*, const u64*, u64
                                   const uint8_t*, u64*, u64*, int, u32, u32, int, const u64*);
 typedef void (*ProbeScanKernel)(Model, const u64*, const u64*, u64, LevelCtl*, int, u32, u64*, u64);
 typedef void (*ProbeApplyKernel)(Model, const u64*, const u64*, const u64*, u64, u64*, u64, LevelCtl*);
+typedef void (*RegenBitsKernel)(Model, const u64*, const u64*, u64, u64, const u32*, u32, LevelCtl*, int, u32, u32, u64*, u64, u64*, u64, u64*, u32, u32);
 // Every instantiation of k_expand and k_materialize, by configuration.  The configurations of BASELINE.json (and their small neighbours used by
 // the tests) have instantiations with the model constants folded in; anything else runs the model's generic ones (SPEC % 1000 == 0).
 struct KernelSet {
@@ -203,13 +210,14 @@ struct KernelSet {
   ExpandKernel plain = nullptr, plain5 = nullptr, modes = nullptr, regen_bits = nullptr, insert = nullptr, probe = nullptr;
   ProbeScanKernel scan = nullptr;       // the probe pass of vsr_probe_scan.hpp (then `probe` is null: the instantiation it replaced is not compiled) ...
   ProbeApplyKernel apply = nullptr;     // ... and the kernel that applies what it listed
+  RegenBitsKernel regen = nullptr;      // the regenerating pass over the claim bitmap of vsr_regen_bits.hpp (`regen_bits` stays: the pass it does not take)
 };
 template <int SPEC>
 KernelSet full_set(ExpandKernel plain5 = nullptr) {             // a model-0 configuration with the whole family of unsharded instantiations
   KernelSet k{k_expand<false, SPEC>, k_materialize<SPEC>, k_expand<true, SPEC>, false, k_expand<true, SPEC, EXPAND_PLAIN>, plain5,
               k_expand<true, SPEC, EXPAND_MODES>, k_expand<true, SPEC, EXPAND_REGEN_BITS>, k_expand<true, SPEC, EXPAND_INSERT>};
   // the probe pass: the kernels of vsr_probe_scan.hpp where a record fits 64 words (R <= 3), k_expand's probe-only instantiation elsewhere
-  if constexpr ((SPEC % 1000) / 100 <= 3) { k.scan = k_probe_scan<SPEC>; k.apply = k_probe_apply<SPEC>; }
+  if constexpr ((SPEC % 1000) / 100 <= 3) { k.scan = k_probe_scan<SPEC>; k.apply = k_probe_apply<SPEC>; k.regen = k_regen_bits<SPEC>; }
   else k.probe = k_expand<true, SPEC, EXPAND_PROBE>;
   return k;
 }
@@ -595,6 +603,14 @@ int32_t vsrmc_checker_create(const vsrmc_model* m, const vsrmc_options* o_in, vs
       c->probe_list = nullptr;
     }
   }
+  // VSRMC_NO_REGEN_KERNEL (tests, A/B): the regenerating passes of k_expand's own instantiation.  VSRMC_REGEN_TRIP=<1 .. 64> (tests): so few instances per
+  // trip that nearly every mini-tile takes several and the wave's chunks roll over often — what VSRMC_CCAP is to the work list
+  if (ks.regen && !std::getenv("VSRMC_NO_REGEN_KERNEL")) c->regen_kernel = (void*)ks.regen;
+  if (const char* ev = std::getenv("VSRMC_REGEN_TRIP")) c->regen_trip = (u32)std::max(1, std::min(64, std::atoi(ev)));
+  // VSRMC_REGEN_DST_STATES=<indices> / VSRMC_REGEN_DST_WORDS=<words> (tests): a regenerating pass, whichever kernel runs it, is told that its destination ends
+  // there (never beyond where it really ends), so that a slice sized for the whole buffer runs full (LevelCtl::full) — an error of the pass, like any full slice
+  if (const char* ev = std::getenv("VSRMC_REGEN_DST_STATES")) c->regen_dst_states = (u64)std::max<long long>(2 * VSR_CAND_CAP, std::atoll(ev));
+  if (const char* ev = std::getenv("VSRMC_REGEN_DST_WORDS")) c->regen_dst_words = (u64)std::max<long long>(1 << 17, std::atoll(ev));
   rc = checker_seed(c);
   if (rc) { vsrmc_checker_destroy(c); return rc; }
   *out = c;
@@ -1114,8 +1130,10 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
     u64* const d_words = dst ? dst->words : c->words[nxt];
     u64* const d_off = dst ? dst->off : c->off[nxt];
     u64* const d_fp = dst ? dst->fp : c->lvl_fp;
-    const u64 d_wcap = dst ? dst->words_cap : c->words_cap(nxt);
-    const u64 nx_cap = dst ? dst->cap : c->opt.frontier_states;
+    // (VSRMC_REGEN_DST_STATES / _WORDS, test knobs: a regenerating pass is handed less of its destination than the slice was sized for, so that it runs full)
+    const bool cut_dst = mode == MODE_REGEN && !io;
+    const u64 d_wcap = std::min<u64>(dst ? dst->words_cap : c->words_cap(nxt), cut_dst && c->regen_dst_words ? c->regen_dst_words : ~(u64)0);
+    const u64 nx_cap = std::min<u64>(dst ? dst->cap : c->opt.frontier_states, cut_dst && c->regen_dst_states ? c->regen_dst_states : ~(u64)0);
     unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)c->num_cus * fs.blocks_per_cu);
     grid = (unsigned)std::max<u64>(1, std::min<u64>(grid, std::min<u64>(nx_cap / (4 * (u64)VSR_CAND_CAP), d_wcap / (4 * 16384))));
     const u64 wmin = std::max<u64>(16384, (u64)ccap * (u64)(fs.stride + 5));   // see phase_expand
@@ -1137,7 +1155,28 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
       else if (mode == MODE_INSERT && c->insert_kernel) kern = c->insert_kernel;
     }
     if (claim_bits && kern != c->regen_bits_kernel && kern != c->insert_kernel) { claim_bits = nullptr; claim_w = 0; }   // (only those two know the bitmap)
+    // ... or, where the configuration has it, the pass's own kernel (vsr_regen_bits.hpp): a wave per mini-tile of 16 parents and chunks of the destination per
+    // wave — their sizes below.  A destination too small for four chunks of either kind per wave of one block keeps k_expand's instantiation.
+    if (kern == c->regen_bits_kernel && claim_bits && c->regen_kernel && fs.tile == 64 && claim_w <= (u64)RGB_ROW_WORDS && c->lds_stride <= 65) {
+      const size_t dyn = rgb_lds_bytes(fs.stride);
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, c->regen_kernel, VSR_BLOCK, dyn) != hipSuccess || nb < 1) return fail(VSRMC_E_HIP, "k_regen_bits: no resident block");
+      const u64 nmt = (n_parents + RGB_MT - 1) / RGB_MT;
+      const u64 wmin_w = (u64)64 * (u64)c->lds_stride;           // a trip's children fit a fresh word chunk: 64 records of the longest kind
+      u64 rgrid = std::max<u64>(1, std::min<u64>((nmt + 3) / 4, (u64)c->num_cus * (u64)std::min(nb, (int)VSR_OCC)));
+      rgrid = std::max<u64>(1, std::min<u64>(rgrid, std::min<u64>(nx_cap / (16 * 64), d_wcap / (16 * wmin_w))));
+      const u32 r_ichunk = (u32)std::max<u64>(64, std::min<u64>(RGB_ICHUNK, nx_cap / (16 * rgrid)));
+      const u32 r_wchunk = (u32)std::max<u64>(wmin_w, std::min<u64>(RGB_WCHUNK, d_wcap / (16 * rgrid)));
+      if (16 * (u64)r_ichunk <= nx_cap && 16 * (u64)r_wchunk <= d_wcap) {
+        const u32 draw = nmt >= rgrid * 4 * RGB_DRAW * 4 ? (u32)RGB_DRAW : 1u;   // (a small pass draws single mini-tiles: every wave gets work)
+        hipLaunchKernelGGL((RegenBitsKernel)c->regen_kernel, dim3((unsigned)rgrid), dim3(VSR_BLOCK), dyn, c->stream, M, src_words, src_off, n_parents, p_offset,
+                           (const u32*)claim_bits, (u32)claim_w, c->ctl, fs.stride, draw, c->regen_trip, d_words, d_wcap, d_off, nx_cap, d_fp, r_ichunk, r_wchunk);
+        c->regen_launches++;
+        kern = nullptr;
+      }
+    }
     if (use_plain || use_probe) { redo_kern = kern; redo_stride = fs.stride; redo_ichunk = ichunk; redo_wchunk = wchunk; redo_words = d_words; redo_off = d_off; redo_fp = d_fp; redo_wcap = d_wcap; redo_cap = nx_cap; redo_grid = grid; }
+    if (kern) {                                                  // (null: k_regen_bits took the pass, between the same two events)
     hipLaunchKernelGGL((ExpandKernel)kern, dim3(grid), dim3(VSR_BLOCK), lds, c->stream, M, src_words, src_off, n_parents, level, c->opt.rank,
                        c->table, c->tmask, c->pending, c->opt.pending_entries, c->ctl, fs.stride, io ? c->opt.world : 1,
                        io ? io->cand_send : nullptr, io ? io->cand_cap : (u64)0, (u32)VSR_CAND_CAP,
@@ -1145,6 +1184,7 @@ int expand_pass(vsrmc_checker* c, const u64* src_words, const u64* src_off, u64 
                        ichunk, wchunk, tile, ccap, !one_rank ? c->filter : (u64*)claim_bits, !one_rank ? c->fmask : claim_w, io ? c->cand_idx : nullptr, cchunk,
                        mode | ((mode == MODE_PROBE && (c->saw_violation || c->probe_all_actions)) ? (int)MODE_NO_FOOTPRINT : 0), p_offset,
                        (const WSet*)((io && c->opt.world > 1) ? c->d_wset : nullptr), c->wepoch);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
   }

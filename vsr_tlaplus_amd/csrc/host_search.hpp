@@ -114,6 +114,12 @@ int32_t vsrmc_checker_probe_violators(vsrmc_checker* c, uint64_t* fps, uint64_t 
   return 0;
 }
 
+int32_t vsrmc_checker_regen_launches(const vsrmc_checker* c, uint64_t* n) {
+  if (!c || !n) return fail(VSRMC_E_ARG, "NULL argument");
+  *n = c->regen_launches;
+  return 0;
+}
+
 int32_t vsrmc_checker_seen_batch(vsrmc_checker* c, const uint64_t* fps, uint64_t n, int32_t level, uint8_t* seen) {
   if (!c || (n && (!fps || !seen))) return fail(VSRMC_E_ARG, "NULL argument");
   if (n == 0) return 0;

@@ -22,6 +22,7 @@
 #include "vras_parse.hpp"
 #include "vsr_kernels.hpp"
 #include "vsr_probe_scan.hpp"
+#include "vsr_regen_bits.hpp"
 #include "vsr_terminal.hpp"
 #include "vsr_where.hpp"
 #include "vsr_constrain.hpp"
